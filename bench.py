@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Benchmark of the XMC-GAN G+D training step on MI355X (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W          (N > 1: launched by torch.distributed.run)
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]     (N > 1: launched by torch.distributed.run)
 
 A "step" is one ``train_step`` (train_d on 56 images + train_g_d on 56 images per GPU) of the C1
 workload -- 128 px coco_xmc, gf = df = 96, per-GPU batch 56, bf16, EMA off, the frozen ResNet-50 image-contrastive
@@ -15,7 +15,12 @@ inside the graph).
 ``python bench.py --gpus N`` with N > 1 and no torchrun environment re-launches itself under
 ``torch.distributed.run`` (one rank per GPU, 127.0.0.1 rendezvous).
 
-Extra objects on the JSON line:
+A plain run sets up, warms up, times exactly K steps and prints the JSON line (``ms_per_step`` = milliseconds of one timed
+step).  ``--dump-outputs DIR`` writes what the last timed step returned to its caller as DIR/<name>.npy (see
+``step_outputs``); the inputs are seeded, so two builds run with the same arguments can be compared output for output.
+
+Extra objects on the JSON line, measured only with ``--full`` (after the timed steps; ``--no-*`` drop single ones):
+  host_enqueue_ms_per_step -- host time of issuing one more step into an empty queue.
   roofline     -- the dominant kernel family, ``conv_stream_kernel`` / ``conv_phase_kernel`` (bf16 3x3 implicit-GEMM fwd +
                   dgrad; two wave tilings; the launches next to a 2x resampling as four 2x2 convolutions):
                   algorithmic FLOPs (2*M*K*N per launch with M = the conv's own output pixels, before any
@@ -153,14 +158,47 @@ def cpu_baseline(cfg, per_device_batch=8, timed=3):
 
 
 def _self_launch(args):
-    """``python bench.py --gpus N`` (N > 1) outside torchrun: re-exec under torch.distributed.run, one rank per GPU."""
+    """``python bench.py --gpus N`` (N > 1) outside torchrun: run under torch.distributed.run as a child, one rank per GPU."""
     import socket
+    import subprocess
     with socket.socket() as sk:
         sk.bind(("127.0.0.1", 0))
         port = sk.getsockname()[1]
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={args.gpus}",
            "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:]
-    os.execv(sys.executable, cmd)
+    sys.exit(subprocess.call(cmd))
+
+
+DUMP_SAMPLE = 1 << 21          # values kept of each flat parameter / Adam-moment arena (tens of millions each at C1)
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def step_outputs(state, metrics, ema=False):
+    """What a caller of the timed step received from its last call, as host float32 / float64 arrays by name: the losses
+    (float64 scalars), G's BatchNorm running statistics and D's spectral-norm vectors in full, and a fixed, seeded sample
+    of ``DUMP_SAMPLE`` positions of each flat arena -- parameters, both Adam moments, the EMA parameters when EMA is on."""
+    import numpy as np
+    from xmcgan_image_generation_amd import synthetic as syn
+    out = {k: np.float64(float(v)) for k, v in metrics.items()}
+
+    def tree(t):
+        return torch.cat([v.detach().reshape(-1).float() for _, v in sorted(syn.tree_leaves(t), key=lambda kv: kv[0])]).cpu().numpy()
+
+    out["g_batch_stats"] = tree(state.generator_state["batch_stats"])
+    out["d_spectral_norm_stats"] = tree(state.discriminator_state["spectral_norm_stats"])
+    for net, opt in (("g", state.g_optimizer), ("d", state.d_optimizer)):
+        arena = opt.arena
+        n = arena.params.numel()
+        pos = np.sort(np.random.default_rng(0).choice(n, size=min(n, DUMP_SAMPLE), replace=False))
+        idx = torch.from_numpy(pos).to(arena.params.device)
+        bufs = {"params": arena.params, "adam_m": arena.m, "adam_v": arena.v}
+        if ema and net == "g":
+            bufs["ema_params"] = state.ema_buffer
+        for name, buf in bufs.items():
+            out[f"{net}_{name}"] = buf.index_select(0, idx).float().cpu().numpy()
+    total = sum(np.asarray(v).nbytes for v in out.values())
+    assert total <= DUMP_LIMIT_BYTES, f"step outputs take {total} bytes, more than {DUMP_LIMIT_BYTES}"
+    return out
 
 
 def _pmc_traffic(kernel_prefixes):
@@ -206,10 +244,16 @@ def main():
     ap.add_argument("--grad-schedule", default="auto", choices=["auto", "overlapped", "exclusive"],
                     help="N > 1: when the gradient exchanges are issued (dp.GradSync.schedule).  auto = time 3 steps of each schedule "
                          "during warm-up and keep the faster (the choice is printed in the JSON line)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-instrument", action="store_true", help="skip the instrumented extra step (roofline)")
-    ap.add_argument("--no-gd-only", action="store_true", help="skip the second timed workload (the G/D step alone)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned as DIR/<name>.npy (float32 / float64, at most 64 MB)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure host_enqueue_ms_per_step, roofline, gd_only and cpu_baseline (off: the headline only)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without cpu_baseline")
+    ap.add_argument("--no-instrument", action="store_true", help="--full without the instrumented extra step (roofline)")
+    ap.add_argument("--no-gd-only", action="store_true", help="--full without the second timed workload (the G/D step alone)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "RANK" not in os.environ:
         _self_launch(args)
@@ -262,8 +306,9 @@ def main():
         # forward on the 2B real + generated images, data gradient on the B generated ones (true 224^2 geometry)
         step_tflop += 3 * b * resnet_v1.forward_flops_per_image() / 1e12
 
-    def time_workload(cfg, additional_data):
-        """state -> one eager step -> capture -> warm-up -> EXACTLY args.steps timed steps between barrier + synchronize"""
+    def time_workload(cfg, additional_data, dump=False):
+        """state -> one eager step -> capture -> warm-up -> EXACTLY args.steps timed steps between barrier + synchronize
+        (``dump``: what the last of them returned, copied to the host before anything else runs)"""
         gen, disc, state = train_utils.create_train_state(cfg, 0)          # identical init on every rank
         batch = syn.make_batch(cfg, per_device_batch=b, rank=rank)         # independent per-rank data
         tb = {k: torch.as_tensor(v).cuda() for k, v in batch.items()}
@@ -354,14 +399,21 @@ def main():
             torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
             dt = float(t)
         losses = {k: round(float(v), 4) for k, v in metrics.items()}
-        # host cost of issuing ONE step into an empty queue (no back-pressure): what the host needs per step
-        fence()
-        t1 = time.perf_counter()
-        state, metrics = step(state)
-        host_one = (time.perf_counter() - t1) * 1e3
-        fence()
+        outputs = None
+        if dump:
+            state = xmc_gan._flush(state)              # N > 1 eager: apply the D update the last step left in flight
+            if rank == 0:
+                outputs = step_outputs(state, metrics, ema=cfg.get("ema", True))
+        host_one = None
+        if args.full:
+            # host cost of issuing ONE step into an empty queue (no back-pressure): what the host needs per step
+            fence()
+            t1 = time.perf_counter()
+            state, metrics = step(state)
+            host_one = round((time.perf_counter() - t1) * 1e3, 3)
+            fence()
         return dict(dt=dt, t_host=t_host, host_one=host_one, losses=losses, graphed=graphed, graph_note=graph_note,
-                    state=state, gen=gen, eager_step=eager_step)
+                    state=state, gen=gen, eager_step=eager_step, outputs=outputs)
 
     def fence():
         if grad_sync is not None:
@@ -369,16 +421,22 @@ def main():
         torch.cuda.synchronize()
 
     sched_info = {}
-    r = time_workload(cfg, additional_data)
+    r = time_workload(cfg, additional_data, dump=args.dump_outputs is not None)
     dt, t_host, host_one, losses, graphed, graph_note = (r[k] for k in ("dt", "t_host", "host_one", "losses", "graphed", "graph_note"))
     state, gen, eager_step = r["state"], r["gen"], r["eager_step"]
     ms = dt / args.steps * 1e3
     value = b * world * args.steps / dt
+    if r["outputs"] is not None:
+        import numpy as np
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for name, arr in r["outputs"].items():
+            np.save(os.path.join(args.dump_outputs, f"{name}.npy"), arr)
+        r["outputs"] = None
 
     # ---- instrumented eager extra step (outside the timed region): per-kernel HIP-event durations
     peak = PEAK_BF16_TFLOPS if cfg.dtype == "bfloat16" else PEAK_F32_TFLOPS
     roofline = None
-    if not args.no_instrument:
+    if args.full and not args.no_instrument:
         # the instrumented step runs SERIALLY (one stream: no overlapped pullbacks, no prefetched generator forward, no
         # async weight gradients), so every event pair brackets exactly one kernel running alone on the GPU -- the
         # same conditions as the committed rocprofv3 kernel trace (tools/profile_round.sh)
@@ -444,7 +502,7 @@ def main():
     # ---- the G/D step alone (BASELINE.json's 40 % target is defined on its 24.93 TFLOP): same harness, same run,
     #      ResNet-50 term off -- a driver-timed number for that workload next to the reference-default headline
     gd_only = None
-    if cfg.pretrained_image_contrastive and args.config == "c1" and world == 1 and not args.no_gd_only:
+    if args.full and cfg.pretrained_image_contrastive and args.config == "c1" and world == 1 and not args.no_gd_only:
         del r, graphed, eager_step, state
         torch.cuda.empty_cache()
         cfg_gd = cfg.copy()
@@ -473,14 +531,14 @@ def main():
                       "global_batch": b * world, "parallelism": f"dp{world}"},
            "launch_mode": launch_mode,
            "grad_schedule": dict(sched_info) if sched_info else None,
-           "host_enqueue_ms_per_step": round(host_one, 3),
+           "host_enqueue_ms_per_step": host_one,
            "host_ms_per_step_in_timed_loop": round(t_host / args.steps * 1e3, 3),
            "losses": losses,
            "roofline": roofline}
     if gd_only is not None:
         out["gd_only"] = gd_only
     if rank == 0:
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(cfg)
         print(json.dumps(out), flush=True)
     if grad_sync is not None:

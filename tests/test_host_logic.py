@@ -441,3 +441,31 @@ def test_bench_reads_the_newest_committed_profile_summaries():
     assert fam is not None and fam["source"].startswith("profiles/r") and "conv3x3_fwd_dgrad" in fam["families"]
     traffic, src = b._pmc_traffic(("conv_stream_kernel", "conv_phase4_kernel", "conv_phase_kernel"))
     assert traffic and traffic > 1e7 and src.startswith("profiles/r") and src >= "profiles/r06"
+
+
+def test_bench_step_outputs_are_the_step_results_at_fixed_positions(stepped):
+    """bench.py --dump-outputs: the losses, the full running statistics, and the SAME seeded positions of every flat arena on
+    every call -- float32 / float64 only, within the 64 MB the option promises"""
+    import importlib.util
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(root, "bench.py"))
+    b = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(b)
+    cfg, new_state, metrics = stepped[:3]
+    out = b.step_outputs(new_state, metrics, ema=True)
+    again = b.step_outputs(new_state, metrics, ema=True)
+    assert set(out) == set(metrics) | {"g_batch_stats", "d_spectral_norm_stats", "g_params", "g_adam_m", "g_adam_v", "g_ema_params",
+                                       "d_params", "d_adam_m", "d_adam_v"}
+    assert all(np.asarray(v).dtype in (np.float32, np.float64) for v in out.values())
+    assert sum(np.asarray(v).nbytes for v in out.values()) <= b.DUMP_LIMIT_BYTES
+    assert all(np.array_equal(out[k], again[k]) for k in out)
+    for k, v in metrics.items():
+        assert out[k] == float(v)
+    assert out["g_batch_stats"].size == sum(t.numel() for _, t in syn.tree_leaves(new_state.generator_state["batch_stats"]))
+    for net, opt in (("g", new_state.g_optimizer), ("d", new_state.d_optimizer)):
+        p = opt.arena.params
+        assert out[f"{net}_params"].size == min(p.numel(), b.DUMP_SAMPLE)
+        pos = np.sort(np.random.default_rng(0).choice(p.numel(), size=min(p.numel(), b.DUMP_SAMPLE), replace=False))
+        assert np.array_equal(out[f"{net}_params"], p[torch.from_numpy(pos)].numpy())
+        assert np.array_equal(out[f"{net}_adam_v"], opt.arena.v[torch.from_numpy(pos)].numpy())
+    assert "g_ema_params" not in b.step_outputs(new_state, metrics, ema=False)

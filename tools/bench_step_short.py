@@ -2,7 +2,7 @@
 """One-line step timing for A/B runs: ms/step of the default workload and of the G/D step alone (graph replay)."""
 import json, subprocess, sys, os
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--no-cpu-baseline", "--steps", "20"] + sys.argv[1:],
+out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--no-cpu-baseline", "--steps", "20"] + sys.argv[1:],
                      capture_output=True, text=True).stdout.strip().splitlines()[-1]
 d = json.loads(out)
 r = d.get("roofline") or {}

@@ -15,6 +15,6 @@ for r in 1 2; do for v in nopre pre; do
   cp /tmp/lib_$v.so $L
   echo "== mask words $v (round $r)"
   timeout 200 python tools/bench_mask_bits.py 2>&1 | grep -v amdgpu
-  timeout 300 python bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-instrument 2>/dev/null | tail -1 | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('step', d['ms_per_step'], 'gd_only', d['gd_only']['ms_per_step'])"
+  timeout 300 python bench.py --full --steps 20 --warmup 3 --no-cpu-baseline --no-instrument 2>/dev/null | tail -1 | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('step', d['ms_per_step'], 'gd_only', d['gd_only']['ms_per_step'])"
 done; done
 cp /tmp/lib_pre.so $L

@@ -10,5 +10,5 @@ timeout 600 python -m pytest tests/test_gpu_kernels.py -q -m gpu -k "conv_phase 
 for r in $(seq $N); do for x in 0 1; do
   echo "== $V=$x (round $r)"
   env $V=$x timeout 300 python tools/bench_phase.py --only-phase --iters 3 2>&1 | grep -v amdgpu | awk '{print $1,$2,$3,"| fwd",$9,$10,"| dgrad",$18,$19}'
-  env $V=$x timeout 300 python bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-instrument 2>/dev/null | tail -1 | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('step', d['ms_per_step'], 'gd_only', d['gd_only']['ms_per_step'])"
+  env $V=$x timeout 300 python bench.py --full --steps 20 --warmup 3 --no-cpu-baseline --no-instrument 2>/dev/null | tail -1 | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('step', d['ms_per_step'], 'gd_only', d['gd_only']['ms_per_step'])"
 done; done

@@ -2,7 +2,7 @@
 R=$PWD; O=$R/gpurun_out/boxes; mkdir -p $O
 export PYTHONPATH=$R
 T=$(date +%H%M%S)
-timeout 600 python bench.py --steps 20 --warmup 3 --no-cpu-baseline 2>/dev/null | tail -1 > $O/bench_$T.json
+timeout 600 python bench.py --full --steps 20 --warmup 3 --no-cpu-baseline 2>/dev/null | tail -1 > $O/bench_$T.json
 python -c "
 import json,sys
 d=json.loads(open('$O/bench_$T.json').read())
