@@ -38,7 +38,7 @@ extern "C" {
 #define XMC_F32 0
 #define XMC_BF16 1
 
-#define XMC_ABI_VERSION 22
+#define XMC_ABI_VERSION 23
 int xmc_abi_version(void);
 
 /* Launch-heuristic knobs -- split-K workgroup targets and tile-selection thresholds whose defaults were A/B'd inside the
@@ -648,6 +648,34 @@ int xmc_subsample2(void* large, void* small, int32_t n, int32_t hc, int32_t wc, 
 int xmc_add_relu(const void* a, const void* b, void* o, int64_t n, int32_t dtype, void* stream);
 int xmc_relu_bwd(const void* dy, const void* dy2, const void* out, void* g, int64_t n, int32_t dtype,
                  void* stream);
+
+/* -------------------------------------------------------- Inception-v3 feature path (FID / Inception Score)
+ * xmcgan/utils/inception_arch.py, inception_utils.py:102-130, eval_metrics.py.  Feature maps 299^2 .. 8^2 in their true
+ * sizes (no canvases); eval-mode BatchNorm is folded into the weights and biases by the caller.  dtype = XMC_F32 | XMC_BF16.
+ *  - xmc_inception_conv: y[:, :, :, y_off : y_off + cout] (rows of ldy elements) = act(conv(x[:, :, :, x_off : x_off + cin]
+ *    (rows of ldx elements), w) + bias), act = ReLU when relu != 0.  w: [cout][kh * kw][cin] in `dtype`, bias float32 (may
+ *    be NULL).  kh, kw in 1..7, stride 1 or 2, pad_t / pad_l zero rows / columns before the input (SAME at stride 1:
+ *    (k - 1) / 2; VALID: 0), any hi, wi, ho, wo.  cout, cin, ldx, ldy, x_off, y_off multiples of 8 (XMC_EINVAL otherwise),
+ *    except first = 1: the network's first layer (cin < 8, contiguous input, no padding), whose gather applies
+ *    clip(2 x - 1, -1, 1) to every loaded value (inception_utils.py:125-127).  Fixed tiles, no split-K: the summation
+ *    order of an output depends on the layer geometry only, never on n.  Channels outside the slice are not written.
+ *  - xmc_maxpool3x3s2_valid: nn.max_pool((3, 3), (2, 2), "VALID") of x (n, hi, wi, c) into the channel slice
+ *    [y_off, y_off + c) of y (n, (hi - 3) / 2 + 1, (wi - 3) / 2 + 1, ldy); c, ldy, y_off multiples of 8.
+ *  - xmc_avgpool3x3_same: tensorflow_style_avg_pooling(x, (3, 3), (1, 1), "SAME") (inception_arch.py:48-67): the sum over
+ *    the in-bounds taps divided by their count; x, y (n, h, w, c), c % 8 == 0, x != y.
+ *  - xmc_mean_hw: y[i][ch] = mean over the hw pixels of x[i] (n, hw, c) -> float32, summed in pixel order per image. */
+typedef struct {
+    int32_t n, hi, wi, cin;   /* x rows: (n, hi, wi) pixels of ldx elements, channels [x_off, x_off + cin) */
+    int32_t ho, wo, cout;     /* y rows: (n, ho, wo) pixels of ldy elements, channels [y_off, y_off + cout) */
+    int32_t kh, kw, stride, pad_t, pad_l;
+    int32_t ldx, x_off, ldy, y_off;
+    int32_t relu, first, dtype;
+} xmc_iconv_desc;
+int xmc_inception_conv(const xmc_iconv_desc* d, const void* x, const void* w, const float* bias, void* y, void* stream);
+int xmc_maxpool3x3s2_valid(const void* x, void* y, int32_t n, int32_t hi, int32_t wi, int32_t c, int32_t ldy,
+                           int32_t y_off, int32_t dtype, void* stream);
+int xmc_avgpool3x3_same(const void* x, void* y, int32_t n, int32_t h, int32_t w, int32_t c, int32_t dtype, void* stream);
+int xmc_mean_hw(const void* x, float* y, int32_t n, int32_t hw, int32_t c, int32_t dtype, void* stream);
 
 #ifdef __cplusplus
 }

@@ -18,7 +18,7 @@ LIB_PATH = os.path.join(_HERE, "libxmcgan_hip.so")
 PROBE_LIB_PATH = os.path.join(_HERE, "libxmc_probe.so")
 
 XMC_F32, XMC_BF16 = 0, 1
-ABI_VERSION = 22
+ABI_VERSION = 23
 
 
 class ConvDesc(C.Structure):
@@ -27,6 +27,12 @@ class ConvDesc(C.Structure):
                [("alpha", C.c_float), ("res_scale", C.c_float), ("w_packed", C.c_int32), ("pool_out", C.c_int32),
                 ("relu_out", C.c_int32), ("mask_after_res", C.c_int32), ("valid_h", C.c_int32), ("valid_w", C.c_int32),
                 ("alpha_dev", C.c_void_p)]
+
+
+class IconvDesc(C.Structure):        # mirrors xmc_iconv_desc
+    _fields_ = [(n, C.c_int32) for n in
+                ("n", "hi", "wi", "cin", "ho", "wo", "cout", "kh", "kw", "stride", "pad_t", "pad_l",
+                 "ldx", "x_off", "ldy", "y_off", "relu", "first", "dtype")]
 
 
 class WgradDesc(C.Structure):
@@ -152,6 +158,10 @@ SIGNATURES = {
     "xmc_adam_wprep_tiles": [_P, _I, _I, _P, _P, _P, _P, _P, _F, C.c_double, C.c_double, _F, _P, _F, _F, _I, _P, _P, _P, _P, _P, _P, _P, _P,
                              _P, _P],
     "xmc_adam_ema_dev_sn": [_P, _P, _P, _P, _P, _L, _F, C.c_double, C.c_double, _F, _P, _F, _F, _I, _P, _P, _I, _P, _P, _P, _P, _P],
+    "xmc_inception_conv": [C.POINTER(IconvDesc), _P, _P, _P, _P, _P],
+    "xmc_maxpool3x3s2_valid": [_P, _P, _I, _I, _I, _I, _I, _I, _I, _P],
+    "xmc_avgpool3x3_same": [_P, _P, _I, _I, _I, _I, _I, _P],
+    "xmc_mean_hw": [_P, _P, _I, _I, _I, _I, _P],
 }
 
 # diagnostic probes: include/xmc_probe.h, libxmc_probe.so (csrc_probe/) -- outside the product ABI

@@ -38,6 +38,8 @@ def get_config() -> ConfigDict:
     c.image_size = 128
     c.batch_size = 56
     c.eval_batch_size = 7
+    c.eval_num = 30000              # images per FID / IS evaluation (coco_xmc.py:23)
+    c.eval_avg_num = 3              # evaluation passes averaged (coco_xmc.py:24)
     c.df_dim = 96
     c.gf_dim = 96
     c.z_dim = 128
@@ -68,6 +70,8 @@ def get_test_config() -> ConfigDict:
     c.pretrained_image_contrastive = False      # build-side: the G/D parity tests run without the ResNet-50 term;
     c.batch_size = 4                            # tests/test_resnet.py and tests/test_gpu_resnet.py switch it on
     c.eval_batch_size = 2
+    c.eval_num = 2                  # coco_xmc.py:76-77
+    c.eval_avg_num = 1
     c.show_num = 4                  # coco_xmc.py:85
     c.df_dim = 16
     c.gf_dim = 16

@@ -1380,6 +1380,53 @@ class HipOps:
               "xmc_relu_bwd")
         return g
 
+    # ------------------------------------------------------- Inception-v3 feature path (FID / Inception Score)
+    def inception_resize(self, x, out):
+        """(n, hs, ws, c) -> bilinear (half-pixel centres) into ``out`` (n, hd, wd, c): the whole of ``out`` is the image"""
+        n, hs, ws, c = x.shape
+        hd, wd = out.shape[1], out.shape[2]
+        assert out.dtype == x.dtype and out.shape[0] == n and out.shape[3] == c
+        check(self.lib.xmc_resize_bilinear(_p(x), _p(out), n, hs, ws, c, hd, wd, hd, wd, 0, _code(x.dtype), self._stream()),
+              "xmc_resize_bilinear")
+        return out
+
+    def inception_conv(self, x, w, bias, out, *, kh, kw, stride=1, pad=(0, 0), x_off=0, y_off=0, relu=True, first=False):
+        """relu(conv(x[..., x_off : x_off + cin], w) + bias) into out[..., y_off : y_off + cout] (xmc_inception_conv):
+        x (n, hi, wi, ldx), w (cout, kh * kw, cin) in the activation dtype, bias float32, out (n, ho, wo, ldy);
+        ``first``: the network's first layer (clip(2x - 1, -1, 1) in the gather)"""
+        n, hi, wi, ldx = x.shape
+        cout, taps, cin = w.shape
+        assert taps == kh * kw and x.dtype == w.dtype == out.dtype and out.shape[0] == n
+        d = _lib.IconvDesc(n=n, hi=hi, wi=wi, cin=cin, ho=out.shape[1], wo=out.shape[2], cout=cout, kh=kh, kw=kw, stride=stride,
+                           pad_t=pad[0], pad_l=pad[1], ldx=ldx, x_off=x_off, ldy=out.shape[3], y_off=y_off, relu=int(relu),
+                           first=int(first), dtype=_code(x.dtype))
+        check(self.lib.xmc_inception_conv(C.byref(d), _p(x), _p(w), _p(bias), _p(out), self._stream()), "xmc_inception_conv")
+        return out
+
+    def maxpool3x3s2_valid(self, x, out, y_off=0):
+        """3x3 stride-2 VALID max pool of x (n, h, w, c) into out[..., y_off : y_off + c]"""
+        n, h, w, c = x.shape
+        assert out.dtype == x.dtype and out.shape[:3] == (n, (h - 3) // 2 + 1, (w - 3) // 2 + 1)
+        check(self.lib.xmc_maxpool3x3s2_valid(_p(x), _p(out), n, h, w, c, out.shape[3], y_off, _code(x.dtype), self._stream()),
+              "xmc_maxpool3x3s2_valid")
+        return out
+
+    def avgpool3x3_same(self, x, out=None):
+        """3x3 stride-1 SAME average pool, divisor = in-bounds taps (TF's avg_pool)"""
+        n, h, w, c = x.shape
+        out = self.empty(x.shape, x.dtype) if out is None else out
+        assert out.shape == x.shape and out.dtype == x.dtype
+        check(self.lib.xmc_avgpool3x3_same(_p(x), _p(out), n, h, w, c, _code(x.dtype), self._stream()), "xmc_avgpool3x3_same")
+        return out
+
+    def mean_hw(self, x, out=None):
+        """(n, h, w, c) -> float32 (n, c): per-image spatial mean in a fixed order (independent of n)"""
+        n, h, w, c = x.shape
+        out = self.empty((n, c), torch.float32) if out is None else out
+        assert out.dtype == torch.float32 and out.shape == (n, c)
+        check(self.lib.xmc_mean_hw(_p(x), _p(out), n, h * w, c, _code(x.dtype), self._stream()), "xmc_mean_hw")
+        return out
+
     def probe_layouts(self):
         out = self.zeros((2 * 64 * 16 + 64 * 4,))
         check(_lib.load_probe().xmc_probe_layouts(_p(out), self._stream()), "xmc_probe_layouts")      # libxmc_probe.so: diagnostics

@@ -1,0 +1,171 @@
+"""FID and Inception Score of a generator (the reference's ``xmcgan/utils/eval_metrics.py``, its ``test`` mode).
+
+``EvalMetric`` mirrors the reference's class: the real images' Inception pools are computed once in the constructor
+(``eval_num // eval_batch_size + 1`` batches of ``next(ds)["image"]``, truncated to ``eval_num``);
+``calculate_inception_fid`` runs ``eval_avg_num`` passes over as many batches of generated images -- from the current and
+from the EMA generator parameters, ``train_utils.eval_step`` -- and returns the 8-tuple
+``(fid, fid_std, is, is_std, ema_fid, ema_fid_std, ema_is, ema_is_std)`` (mean and std over the passes).
+
+Seeds.  The reference draws z with ``jax.random.fold_in(fold_in(rng, pass), step)``, split over the local devices.  Here
+the z of pass ``i``, batch ``step`` on rank ``r`` comes from ``torch.Generator().manual_seed(seed)`` (inside ``eval_step``)
+with ``seed = SeedSequence([rng, i, step, r]).generate_state(1, uint64)[0] >> 1``: a pure function of ``(rng, pass, step,
+rank)``, so two calls with the same ``rng`` see the same z.
+
+Batching.  Images are buffered so that Inception runs on chunks of ``chunk`` images whatever ``eval_batch_size`` is (at the
+reference's 7 images per batch the 8 x 8 layers would fill a few of the 256 CUs).  The kernels' summation order does not
+depend on the chunk, so an image's pool is the same however the evaluation batches it.
+
+With a ``group`` (``torch.distributed``), every rank draws its own batches, and pools and predictions are all-gathered in
+rank-major order before truncation -- the reference's ``lax.all_gather`` + reshape: every rank returns the same numbers.
+"""
+from __future__ import annotations
+
+import warnings
+
+import numpy as np
+import torch
+
+from . import inception_utils
+
+
+def batch_seed(rng, pass_index, step, rank=0):
+    """the integer seed of generated batch ``step`` of pass ``pass_index`` on ``rank`` (module docstring)"""
+    state = np.random.SeedSequence([int(rng) & 0xFFFFFFFFFFFFFFFF, int(pass_index), int(step), int(rank)])
+    return int(state.generate_state(1, np.uint64)[0] >> np.uint64(1))
+
+
+def _images(x):
+    return x.detach().float() if isinstance(x, torch.Tensor) else np.asarray(x, np.float32)
+
+
+class _Chunker:
+    """collects images and runs ``inception`` on full chunks of ``chunk`` images (the tail on what is left)"""
+
+    def __init__(self, inception, chunk):
+        self.inception, self.chunk = inception, int(chunk)
+        self.pending, self.count, self.pools, self.preds = [], 0, [], []
+
+    def add(self, images):
+        self.pending.append(images)
+        self.count += images.shape[0]
+        while self.count >= self.chunk:
+            self._run(self.chunk)
+
+    def _run(self, n):
+        take, left, got = [], [], 0
+        for im in self.pending:
+            if got >= n:
+                left.append(im)
+                continue
+            k = min(n - got, im.shape[0])
+            take.append(im[:k])
+            if k < im.shape[0]:
+                left.append(im[k:])
+            got += k
+        self.pending, self.count = left, self.count - got
+        if isinstance(take[0], torch.Tensor):
+            images = take[0] if len(take) == 1 else torch.cat(take, 0)
+        else:
+            images = take[0] if len(take) == 1 else np.concatenate(take, 0)
+        pool, preds = self.inception(images)
+        self.pools.append(np.asarray(pool, np.float32))
+        self.preds.append(np.asarray(preds, np.float32))
+
+    def finish(self):
+        if self.count:
+            self._run(self.count)
+        return np.concatenate(self.pools, 0), np.concatenate(self.preds, 0)
+
+
+class EvalMetric:
+    """FID / Inception Score evaluation (eval_metrics.py:31-216).
+
+    ``ds``: iterator of batches (``next(ds)["image"]`` (B, H, W, 3) in [0, 1], plus the caption fields ``eval_step`` needs);
+    ``config``: ``eval_num``, ``eval_batch_size``, ``eval_avg_num``; ``inception_ckpt_path``: see
+    ``inception_utils.inception_model`` (``None`` = random weights, whose FID means nothing); ``ops``: a ``HipOps`` (default: a
+    new one in ``dtype``); ``dtype``: float32 as the reference, bf16 opt-in; ``inception``: any callable
+    ``images -> (pool, preds)`` in place of the HIP network; ``chunk``: images per Inception launch sequence; ``group``: a
+    ``torch.distributed`` process group."""
+
+    def __init__(self, ds, config, num_splits=1, inception_ckpt_path=None, *, ops=None, dtype=torch.float32, inception=None,
+                 chunk=256, group=None):
+        self.ds = ds
+        self.config = config
+        self.eval_num = int(config.eval_num)
+        self.eval_batch_size = int(config.eval_batch_size)
+        self.avg_num = int(config.eval_avg_num)
+        self.num_splits = num_splits
+        self.chunk = chunk
+        self.group = group
+        if inception is None:
+            if inception_ckpt_path is None:
+                warnings.warn("EvalMetric: random Inception-v3 weights (inception_ckpt_path=None): FID and IS from them mean "
+                              "nothing; convert the real weights and pass their path", stacklevel=2)
+            if ops is None:
+                from ..ops import HipOps
+                ops = HipOps(dtype=dtype)
+            state = inception_utils.inception_model(inception_ckpt_path)
+            inception = inception_utils.InceptionV3Features(ops, state["params"], state["batch_stats"])
+        self.inception = inception
+        self._pool = self._get_real_pool_for_evaluation()
+
+    @property
+    def n_iter(self):
+        return self.eval_num // self.eval_batch_size + 1
+
+    def _rank(self):
+        if self.group is None:
+            return 0
+        import torch.distributed as dist
+        return dist.get_rank(self.group)
+
+    def _gather(self, a):
+        """all-gather an (n, d) array over the group, rank-major (the reference's all_gather + reshape)"""
+        if self.group is None:
+            return a
+        import torch.distributed as dist
+        world = dist.get_world_size(self.group)
+        dev = torch.device("cpu") if dist.get_backend(self.group) == "gloo" else torch.device("cuda", torch.cuda.current_device())
+        t = torch.as_tensor(np.ascontiguousarray(a)).to(dev)
+        parts = [torch.empty_like(t) for _ in range(world)]
+        dist.all_gather(parts, t, group=self.group)
+        return np.concatenate([p.cpu().numpy() for p in parts], 0)
+
+    def _finish(self, chunker):
+        pool, preds = chunker.finish()
+        return self._gather(pool)[:self.eval_num], self._gather(preds)[:self.eval_num]
+
+    def _get_real_pool_for_evaluation(self):
+        ch = _Chunker(self.inception, self.chunk)
+        for _ in range(self.n_iter):
+            ch.add(_images(next(self.ds)["image"]))
+        pool, _ = self._finish(ch)
+        return pool
+
+    def _get_generated_pool_for_evaluation(self, generator_fn, state, rng):
+        from .. import train_utils
+        ch, ema_ch = _Chunker(self.inception, self.chunk), _Chunker(self.inception, self.chunk)
+        rank = self._rank()
+        pass_index, pass_rng = rng
+        for step in range(self.n_iter):
+            batch = next(self.ds)
+            seed = batch_seed(pass_rng, pass_index, step, rank)
+            image, ema_image = train_utils.eval_step(seed, state, batch, generator_fn, self.config)
+            ch.add(_images(image))
+            ema_ch.add(_images(ema_image))
+        pool, preds = self._finish(ch)
+        ema_pool, ema_preds = self._finish(ema_ch)
+        return pool, preds, ema_pool, ema_preds
+
+    def calculate_inception_fid(self, generator_fn, state, rng):
+        """-> (fid, fid_std, inception_score, inception_score_std, ema_fid, ema_fid_std, ema_inception_score,
+        ema_inception_score_std): mean and std over ``eval_avg_num`` passes (eval_metrics.py:172-216)"""
+        fid_list, is_list, ema_fid_list, ema_is_list = [], [], [], []
+        for i in range(self.avg_num):
+            pool, preds, ema_pool, ema_preds = self._get_generated_pool_for_evaluation(generator_fn, state, (i, rng))
+            is_list.append(inception_utils.calculate_inception_score(preds, num_splits=self.num_splits)[0])
+            ema_is_list.append(inception_utils.calculate_inception_score(ema_preds, num_splits=self.num_splits)[0])
+            fid_list.append(inception_utils.calculate_fid(pool, self._pool))
+            ema_fid_list.append(inception_utils.calculate_fid(ema_pool, self._pool))
+        return (float(np.mean(fid_list)), float(np.std(fid_list)), float(np.mean(is_list)), float(np.std(is_list)),
+                float(np.mean(ema_fid_list)), float(np.std(ema_fid_list)), float(np.mean(ema_is_list)), float(np.std(ema_is_list)))
