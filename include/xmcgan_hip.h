@@ -38,7 +38,7 @@ extern "C" {
 #define XMC_F32 0
 #define XMC_BF16 1
 
-#define XMC_ABI_VERSION 23
+#define XMC_ABI_VERSION 24
 int xmc_abi_version(void);
 
 /* Launch-heuristic knobs -- split-K workgroup targets and tile-selection thresholds whose defaults were A/B'd inside the
@@ -160,17 +160,32 @@ int xmc_conv2d_pw_dual(const xmc_conv_desc* d, const void* x, const void* x2, in
  *   pad; relu != 0 applies max(., 0) first (the `relu_in` of the convolution).
  * xmc_mx8_pack_conv_weight: bf16 fragment-packed weights (xmc_pack_conv_weight / the packed prep outputs: rows x 9 taps x
  *   k) -> w8 (ceil(rows / 32) * ceil(k / 64) * 9 * 2048 bytes) and wscale (ceil(rows / 32) * ceil(k / 64) * 3 * 256 bytes).
+ *   taps = 16 (ABI 24): the input is an "out"-order 16-tap phase copy of xmc_phase_conv_weight / xmc_wprep_batched (tap = phase * 4 +
+ *   tu * 2 + tv; the tap sums were formed in float32 and rounded to bf16 once) -> w8 (ceil(rows / 32) * ceil(k / 64) * 16 * 2048
+ *   bytes) and wscale (ceil(rows / 32) * ceil(k / 64) * 4 * 256 bytes: one scale dword per phase, byte = tu * 2 + tv).
  * xmc_conv2d_mx8: y = epilogue(conv3x3(x8, w8)); d as for xmc_conv2d_nhwc with ks = 3, cin = the TRUE channel count,
  *   relu_in = mask_after_res = valid_* = 0 (relu_out: see xmc_conv2d_mx8_bits); ws (may be NULL) of xmc_conv2d_mx8_workspace_bytes(d) bytes
  *   enables split-K on few-tile layers.  y8 (may be NULL; needs bf16 output, cout % 64 == 0 and a launch without
  *   split-K): the epilogue also writes y as packets for the NEXT convolution, y8_relu = that convolution's relu_in --
  *   byte for byte what xmc_mx8_quantize(y, relu) would write, without the extra pass.
+ * The "out" PHASE form on MX-fp8 operands (ABI 24): d->w_packed = 1 | 16 with d->ups = 1 runs conv3x3(nearest_upsample2(x)) as four
+ *   2x2 convolutions on the low-resolution grid, y[2i+a][2j+b] = sum_{tu,tv} E_ab[tu][tv] x[i+a-1+tu][j+b-1+tv] (16 instead of 36
+ *   block-scaled products per low-resolution pixel); x8 = the packets of the LOW-resolution tensor, w8 / wscale = the taps = 16
+ *   output of xmc_mx8_pack_conv_weight.  Replaces, when config.conv_fp8_phase is set, the generator blocks' first convolution
+ *   (xmcgan/nets/common.py:152-159) and the data gradient of the down-sampling discriminator blocks' second convolution (the
+ *   adjoint of xmcgan/nets/common.py:76-78).  Domain = xmc_conv2d_mx8_phase_supported(d): bf16, ks = 3, ups, no pool_out (the "in"
+ *   form is not built: XMC_EINVAL), cin % 64 == 0, cout % 32 == 0, power-of-two low-resolution grids of 4 x 4 and larger,
+ *   relu_in = res_ups = mask_after_res = valid_* = 0; res must be NULL.  bias, alpha, alpha_dev, mask, mask_bits, y_bits,
+ *   relu_out, out_f32, y8 and the split-K workspace as for the 3x3 form (xmc_conv2d_mx8_workspace_bytes answers for these
+ *   descriptors too).  Outside the domain the launch returns XMC_EINVAL; it never runs another kernel.
  * xmc_mx8_probe: one scaled MFMA on a8 [32][64] / b8 [32][64] (B transposed) bytes with scales as / bs [32][2] ->
  *   d [32][32] float32; pins the operand layout (tests). */
 int xmc_mx8_quantize(const void* x, void* x8, int64_t pixels, int32_t c, int32_t relu, void* stream);
 int xmc_mx8_pack_conv_weight(const void* w_packed, void* w8, void* wscale, int32_t rows, int32_t taps, int32_t k,
                              void* stream);
 int64_t xmc_conv2d_mx8_workspace_bytes(const xmc_conv_desc* d);
+/* 1 when a descriptor with w_packed bits 0 and 4 is inside the MX-fp8 "out" phase kernel's domain, else 0 */
+int xmc_conv2d_mx8_phase_supported(const xmc_conv_desc* d);
 int xmc_conv2d_mx8(const xmc_conv_desc* d, const void* x8, const void* w8, const void* wscale,
                    const float* bias, const void* mask, const void* res, void* y, void* y8, int32_t y8_relu,
                    void* ws, void* stream);

@@ -1,7 +1,10 @@
 """conv3x3 next to a 2x resampling: the 3x3 kernel (ups gather / pooled epilogue) vs four 2x2 convolutions on the low-resolution
 grid (conv_phase_kernel), C1 shapes (B = 56; D at 2B = 112), forward and data gradient, interleaved rounds.
 TF/s are ALGORITHMIC (the 3x3 formulation's 2 M K N); the phase launches execute 4/9 of them.
-usage (GPU box): PYTHONPATH=. python tools/bench_phase.py [--iters 5]"""
+--fp8: the "out"-form rows (G's ups forwards, D's ups data gradients with a 64-multiple reduction) in the MX-fp8 mode instead:
+the MX 3x3 kernel on the upsampled gather, the bf16 phase kernel and the MX phase kernel (ops.fp8_phase_mx), the two MX kernels
+once with the quantisation pass in the launch ("+q") and once on packets that are already there ("pk").
+usage (GPU box): PYTHONPATH=. python tools/bench_phase.py [--iters 5] [--fp8]"""
 import argparse
 import math
 import torch
@@ -11,6 +14,7 @@ ap = argparse.ArgumentParser()
 ap.add_argument("--iters", type=int, default=5)
 ap.add_argument("--batch", type=int, default=56)
 ap.add_argument("--only-phase", action="store_true", help="time only the phase-decomposed forward / data-gradient launches (ablation builds)")
+ap.add_argument("--fp8", action="store_true", help="MX 3x3 vs bf16 phase vs MX phase on the out-form rows")
 args = ap.parse_args()
 ops = HipOps(torch.bfloat16)
 g = torch.Generator().manual_seed(0)
@@ -36,6 +40,58 @@ def timed(fn):
     return e0.elapsed_time(e1) / 10
 
 
+def fp8_rows():
+    """one line per out-form launch: ms of bf16 3x3 | MX 3x3 +q, pk | bf16 phase | MX phase +q, pk | MX phase pk / bf16 phase"""
+    print(f"{'launch':28s} {'GF':>6s} | bf16 3x3 | MX 3x3 +q     pk | bf16 phase | MX phase +q     pk | bf16 phase / MX phase: +q    pk")
+    tot = [0.0] * 6
+    for name, kind, n, lo, cin, cout in LAYERS:
+        w = (torch.randn((cout, 9, cin), generator=g) / math.sqrt(9 * cin)).cuda()
+        k = cin if kind == "ups" else cout               # reduction length of the out-form launch
+        rows = cout if kind == "ups" else cin
+        if k % 64:
+            continue
+        pick = (lambda pair: pair[0]) if kind == "ups" else (lambda pair: pair[1])
+        ops.fp8, ops.fp8_phase, ops.fp8_phase_mx = False, True, False
+        w3 = pick(ops.prep_conv_weight(w, None, True))
+        ops.fp8, ops.fp8_phase = True, False
+        w3x = pick(ops.prep_conv_weight(w, None, True))
+        ops.fp8_phase, ops.fp8_phase_mx = True, True
+        wph = pick(ops.prep_conv_weight(w, None, True, phase=kind))
+        assert w3x.mx8 is not None and wph.phase_mx8 is not None
+        t = torch.randn((n, lo, lo, k), generator=g).cuda().bfloat16()
+        tq = t.clone()
+        tq.mx8 = (ops.quantize_mx8(t), False)
+        if kind == "ups":
+            kw = dict(bias=torch.zeros(rows, device="cuda"))
+        else:
+            kw = dict(bias=None, alpha=0.25, alpha_dev=torch.ones(1, device="cuda"),
+                      mask=torch.randn((n, 2 * lo, 2 * lo, rows), generator=g).cuda().bfloat16())
+
+        def launch(mode, wt, src):
+            ops.fp8, ops.fp8_phase, ops.fp8_phase_mx = mode
+            y = ops.conv(src, wt, kw["bias"], ks=3, ups=True, **{a: b for a, b in kw.items() if a != "bias"})
+            return y
+        variants = [((False, True, False), w3, t, False, False), ((True, False, False), w3x, t, False, False), ((True, False, False), w3x, tq, False, False),
+                    ((True, True, False), wph, t, True, False), ((True, True, True), wph, t, True, True), ((True, True, True), wph, tq, True, True)]
+        for mode, wt, src, ph, mxph in variants:           # every column runs the kernel it is named after
+            launch(mode, wt, src)
+            assert ops.last_conv_phase == ph and ops.last_conv_mx8_phase == mxph, (name, mode)
+        best = [1e9] * 6
+        for r in range(args.iters):
+            for i, (mode, wt, src, _, _) in enumerate(variants):
+                best[i] = min(best[i], timed(lambda: launch(mode, wt, src)))
+        for i in range(6):
+            tot[i] += best[i]
+        fl = 2.0 * n * 4 * lo * lo * k * rows * 9
+        print(f"{name + (' fwd' if kind == 'ups' else ' dgrad'):28s} {fl / 1e9:6.1f} | {best[0]:8.3f} | {best[1]:9.3f} {best[2]:6.3f} | {best[3]:10.3f} |"
+              f" {best[4]:11.3f} {best[5]:6.3f} | {best[3] / best[4]:25.2f} {best[3] / best[5]:5.2f}")
+    print(f"{'TOTAL':28s}        | {tot[0]:8.3f} | {tot[1]:9.3f} {tot[2]:6.3f} | {tot[3]:10.3f} | {tot[4]:11.3f} {tot[5]:6.3f} |"
+          f" {tot[3] / tot[4]:25.2f} {tot[3] / tot[5]:5.2f}")
+
+
+if args.fp8:
+    fp8_rows()
+    raise SystemExit(0)
 print(f"{'layer':22s} {'GF':>6s} | fwd 3x3 ms TF/s | fwd phase ms TF/s    x | dgrad 3x3 ms TF/s | dgrad phase ms TF/s    x | wgrad 3x3 ms TF/s | wgrad phase ms TF/s    x")
 tot = [0.0] * 6
 for name, kind, n, lo, cin, cout in LAYERS:

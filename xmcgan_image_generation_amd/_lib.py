@@ -18,7 +18,7 @@ LIB_PATH = os.path.join(_HERE, "libxmcgan_hip.so")
 PROBE_LIB_PATH = os.path.join(_HERE, "libxmc_probe.so")
 
 XMC_F32, XMC_BF16 = 0, 1
-ABI_VERSION = 23
+ABI_VERSION = 24
 
 
 class ConvDesc(C.Structure):
@@ -144,6 +144,7 @@ SIGNATURES = {
     "xmc_mx8_quantize": [_P, _P, _L, _I, _I, _P],
     "xmc_mx8_pack_conv_weight": [_P, _P, _P, _I, _I, _I, _P],
     "xmc_conv2d_mx8_workspace_bytes": [C.POINTER(ConvDesc)],
+    "xmc_conv2d_mx8_phase_supported": [C.POINTER(ConvDesc)],
     "xmc_conv2d_mx8": [C.POINTER(ConvDesc), _P, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P],
     "xmc_conv2d_mx8_bits": [C.POINTER(ConvDesc), _P, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P],
     "xmc_mx8_probe": [_P, _P, _P, _P, _P, _P],

@@ -60,6 +60,7 @@ def get_config() -> ConfigDict:
     c.show_num = 64                 # images per sampling grid (coco_xmc.py:42)
     # build-side switches (not in the reference)
     c.ema = True
+    c.conv_fp8_phase = False        # with conv_fp8: the "out"-form phase launches (conv3x3(upsample2(.))) on the MX-fp8 phase kernel too
     return c
 
 

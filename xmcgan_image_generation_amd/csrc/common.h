@@ -467,6 +467,7 @@ int xmc_internal_optin_conv_stream(void);
 int xmc_internal_optin_wgrad_dma(void);
 int xmc_internal_optin_wgrad_patch(void);
 int xmc_internal_optin_losses(void);
+int xmc_internal_optin_mx8(void);
 }
 
 // compute units of the current device (cached per device; 256 on MI355X) -- sizes persistent-workgroup grids

@@ -72,6 +72,7 @@ extern "C" int xmc_create(int32_t device, void** handle) {
     if (rc == XMC_OK) rc = xmc_internal_optin_wgrad_dma();
     if (rc == XMC_OK) rc = xmc_internal_optin_wgrad_patch();
     if (rc == XMC_OK) rc = xmc_internal_optin_losses();
+    if (rc == XMC_OK) rc = xmc_internal_optin_mx8();
     (void)hipSetDevice(prev);
     if (rc != XMC_OK) return rc;
     xmc_context* c = new (std::nothrow) xmc_context;

@@ -9,7 +9,8 @@
 //                written by mx8_quantize_kernel from the bf16 tensor (the ReLU of `relu_in` folded in);
 //   weights      fragment order [cout / 32][Cp / 64][tap][piece 0..1][lane 0..63][16 bytes] + scales
 //                [cout / 32][Cp / 64][3][lane] uint32 (byte t % 4 of dword t / 4 = tap t), converted from the bf16
-//                fragment-packed copy the prep kernels already write.
+//                fragment-packed copy the prep kernels already write.  The 16-tap phase copies of the layers next to a 2x
+//                upsampling convert the same way ([tap 0..15], 4 scale dwords: one per phase) for conv_phase_mx8_kernel below.
 //
 // Operand layout of the instruction (measured: tools/mx8_probe_layout.py, pinned by tests/test_gpu_mx8.py): lane l holds
 // row / column l % 32; with h = l / 32 its registers 0..3 (16 bytes) are K = 16 h + 0..15 and its registers 4..7 are
@@ -466,6 +467,247 @@ __global__ __launch_bounds__(256, 2) void conv_stream_mx8_kernel(const S8Args p)
     }
 }
 
+// ---- round 7: the "out" phase form on MX-fp8 operands ----------------------------------------------------------------
+// conv3x3(nearest_upsample2(x)) as four 2x2 convolutions on the LOW-resolution grid (conv_phase_kernel of conv_stream.hip),
+// multiplied by the block-scaled MFMA: y[2i+a][2j+b] = sum_{tu,tv} E_ab[tu][tv] x[i+a-1+tu][j+b-1+tv].  Weights: the MX copy
+// of the 16-tap phase weights (tap = phase * 4 + tu * 2 + tv, phase = 2a + b; the tap sums were formed in float32 and are
+// quantised once, when the weight is prepared).  The kernel is conv_stream_mx8_kernel with the phase as a grid dimension:
+//   * a workgroup = one phase of one tile of 256 LOW-resolution pixels x 128 couts; the four phases of a tile are
+//     neighbours in the launch order, so three of the four patch reads hit the L2;
+//   * the patch is the (Wt + 1) x (Rt + 1) low-resolution packets with origin (y0 + a - 1, x0 + b - 1): whole packets,
+//     linear 16-byte copies as before; at most 400 patch pixels (16 images of 4 x 4), so the 4^2 grids fit too;
+//   * one chunk is 4 K = 64 steps (16 MFMA groups) instead of 9: the ring phase no longer alternates between chunks, and
+//     the 8 patch vectors of the next chunk are staged as two groups of four (loaded at the top of steps 0 / 2, stored at
+//     the end of steps 1 / 3: two steps = 16 MFMAs of slack each), four register sets instead of two;
+//   * a chunk has ONE scale dword per weight block (byte s = tap s of this phase) instead of three;
+//   * the store is stride 2: output pixel (2 (y0 + r) + a, 2 (x0 + c) + b) -- mask, mask bits, y bits and packets are
+//     addressed by that pixel through the shared epilogue.
+// Registers: 128 accumulators + 32 weight ring + 16 B fragments + 16 patch staging; LDS as the 3x3 kernel (2 x 32 KiB patch
+// buffers + 8 KiB parked offsets = 72 KiB, two workgroups per CU).
+__global__ __launch_bounds__(256, 2) void conv_phase_mx8_kernel(const S8Args p) {
+    constexpr int STEPS = 4;                         // taps of one phase: one K = 64 step each per 64-channel chunk
+    constexpr int D = 2;                             // weight register ring depth: slot = step % 2 (STEPS is even)
+    extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
+
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int total_tiles = p.tiles_m * p.tiles_n;
+    const int wid = xcd_remap(blockIdx.x, total_tiles * p.ksplit * 4);
+    const int ph = wid & 3, pa = ph >> 1, pb = ph & 1;
+    const int wrest = wid >> 2;
+    const int split = wrest / total_tiles, tile = wrest - split * total_tiles;
+    const int tn = tile / p.tiles_m, tm = tile - tn * p.tiles_m;
+    const int c_begin = split * p.chunks_per_split;
+    const int c_end = min(p.nchunks, c_begin + p.chunks_per_split);
+    const int Wt = 1 << p.log2_wt, Rt = 1 << p.log2_rt;
+    const int tx = tm & ((1 << p.log2_tx) - 1), rest = tm >> p.log2_tx;
+    const int ty = rest & ((1 << p.log2_ty) - 1);
+    const int img0 = (rest >> p.log2_ty) << p.log2_imgs;
+    const int y0 = ty << p.log2_rt, x0 = tx << p.log2_wt;        // low-resolution origin of the tile
+
+    const __amdgpu_buffer_rsrc_t xr = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p.x), 0, p.x_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t wr = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p.w), 0, p.w_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t wsr = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p.wsc), 0, p.wsc_bytes, 0x00020000);
+    constexpr unsigned OOB = 0xfffffff0u;            // beyond any buffer: the load returns zeros
+
+    // ---- patch staging: as conv_stream_mx8_kernel (vector v = thread + 256 i is vector v % 5 of patch pixel v / 5)
+    const int nvec = p.PP * 5;
+    const int row_bytes = (p.Cp >> 6) * 80;          // one pixel of x8
+    auto patch_voff = [&](int i) -> unsigned {
+        const int v = tid + 256 * i;
+        const int pp = (v * 13108) >> 16, kv = v - pp * 5;               // v / 5 for v < 2^14
+        const int pr = (pp * p.magic_pw) >> 16, pc = pp - pr * p.PW;
+        const int im = (pr * p.magic_pr1) >> 16, rr = pr - im * p.PR1;
+        const int y = y0 + rr + pa - 1, xx = x0 + pc + pb - 1;           // source pixel on the low-resolution map
+        const bool in = (v < nvec) & ((unsigned)y < (unsigned)p.Hi) & ((unsigned)xx < (unsigned)p.Wi) & (img0 + im < p.N);
+        return in ? (unsigned)((((img0 + im) * p.Hi + y) * p.Wi + xx) * row_bytes + kv * 16) : OOB;
+    };
+    unsigned* const pvo_lds = reinterpret_cast<unsigned*>(lds + 2 * PBUF_BYTES) + tid;     // + i * 256
+    auto store_vec = [&](int i, int bufoff, u32x4 q) {
+        *reinterpret_cast<u32x4*>(lds + bufoff + (tid + 256 * i) * 16) = q;
+    };
+
+    // ---- MFMA geometry: wave -> 64 cout x 128 low-resolution pixels (2 x 4 blocks)
+    const int wp = wave >> 1, wc = (wave ^ (blockIdx.x >> 3)) & 1;
+    const int l31 = lane & 31, lhi = lane >> 5;
+    int pbase[4];                                    // LDS byte offset of (lane's pixel, tap (0,0), channels 16 lhi ..) in buffer 0
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const int t = wp * 128 + j * 32 + l31;
+        const int c = t & (Wt - 1), rowi = t >> p.log2_wt;
+        const int im = rowi >> p.log2_rt, rj = rowi & (Rt - 1);
+        pbase[j] = ((im * p.PR1 + rj) * p.PW + c) * SPITCH_B + lhi * 16;
+    }
+    auto out_pixel = [&](int j) {                    // output pixel index of block j's lane (or -1); epilogue only
+        const int t = wp * 128 + j * 32 + l31;
+        const int c = t & (Wt - 1), rowi = t >> p.log2_wt;
+        const int im = rowi >> p.log2_rt, rj = rowi & (Rt - 1);
+        return (img0 + im < p.N) ? ((img0 + im) * p.Ho + 2 * (y0 + rj) + pa) * p.Wo + 2 * (x0 + c) + pb : -1;
+    };
+    const int soff = 64 - 15 * lhi;                  // scale byte of K block lhi (row byte 64 + lhi), relative to pbase
+    // ---- weight stream: block cb = tn * 4 + wc * 2 + i; a chunk holds 16 units (4 phases x 4 taps), this phase's are 4 ph ..
+    const int ncb = (p.Cout + 31) >> 5;
+    unsigned wvoff[2], wsvoff[2];
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+        const int cb = tn * 4 + wc * 2 + i;
+        wvoff[i] = cb < ncb ? ((unsigned)(cb * p.nchunks + c_begin) * 16u + 4u * ph) * 2048u + lane * 16 : OOB;
+        wsvoff[i] = cb < ncb ? ((unsigned)(cb * p.nchunks + c_begin) * 4u + ph) * 256u + lane * 4 : OOB;
+    }
+    v8i wreg[D][2];
+    auto load_w = [&](int slot, int i, int wch, int u) {             // unit u = tap u of this phase in the chunk at byte wch
+        const int off = wch + u * 2048;
+        wreg[slot][i] = join8(__builtin_amdgcn_raw_buffer_load_b128(wr, wvoff[i], off, 0),
+                              __builtin_amdgcn_raw_buffer_load_b128(wr, wvoff[i], off + 1024, 0));
+    };
+    unsigned wsc[2];                                 // this chunk's weight scales: byte s = tap s of this phase
+    auto load_wsc = [&](int cl) {
+#pragma unroll
+        for (int i = 0; i < 2; ++i) wsc[i] = __builtin_amdgcn_raw_buffer_load_b32(wsr, wsvoff[i], cl * 1024, 0);
+    };
+
+    f32x16 acc[2][4];
+    v8i xf[2];                                       // B fragments: q = tap * 4 + j in xf[q & 1], read two fragments ahead
+    unsigned xsc[2];
+    auto read_x = [&](int q, int bufoff) {
+        const int tap = q >> 2, j = q & 3;
+        const int off = bufoff + ((tap >> 1) * p.PW + (tap & 1)) * SPITCH_B;
+        xf[q & 1] = join8(*reinterpret_cast<const u32x4*>(lds + pbase[j] + off), *reinterpret_cast<const u32x4*>(lds + pbase[j] + off + 32));
+        xsc[q & 1] = lds[pbase[j] + off + soff];
+    };
+
+    // ---- prologue: whole patch of chunk 0 -> buffer 0; weight units 0 .. D-1; scales of chunk 0
+    {
+        u32x4 p0[NV_MAX];
+#pragma unroll
+        for (int i = 0; i < NV_MAX; ++i) {
+            const unsigned vo = patch_voff(i);
+            pvo_lds[i * 256] = vo;                   // read back only by this thread: no barrier needed for it
+            p0[i] = __builtin_amdgcn_raw_buffer_load_b128(xr, vo, c_begin * 80, 0);
+        }
+#pragma unroll
+        for (int u = 0; u < D; ++u)
+#pragma unroll
+            for (int i = 0; i < 2; ++i) load_w(u, i, 0, u);
+        load_wsc(0);
+#pragma unroll
+        for (int i = 0; i < NV_MAX; ++i) store_vec(i, 0, p0[i]);
+    }
+    __syncthreads();
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+#pragma unroll
+            for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
+    read_x(0, 0); read_x(1, 0);
+
+    auto k_loop = [&](auto nv_tag) {
+        constexpr int NVB = decltype(nv_tag)::value;
+        for (int chunk = c_begin; chunk < c_end; ++chunk) {
+            const bool next_chunk = chunk + 1 < c_end;
+            const int cl = chunk - c_begin;
+            const int cur = (cl & 1) * PBUF_BYTES, nxt = PBUF_BYTES - cur;
+            const int nsoff = next_chunk ? (chunk + 1) * 80 : 0x7ffffff0;      // (last chunk: out of range, zeros, no traffic)
+            const int wch = cl * 32768;              // this chunk's 16 units
+            // the ring refills of steps 2 / 3 fetch the NEXT chunk's first units; behind the weight's last chunk they re-read this
+            // chunk's instead (unused either way) so that no load leaves the buffer
+            const int wnx = chunk + 1 < p.nchunks ? wch + 32768 : wch;
+            u32x4 pq[4];
+#pragma unroll
+            for (int s = 0; s < STEPS; ++s) {
+                const int slot = s & 1;
+#if !(MX8_ABL & 4)
+                if ((s & 1) == 0) {
+#pragma unroll
+                    for (int v = 0; v < 4; ++v) pq[v] = __builtin_amdgcn_raw_buffer_load_b128(xr, pvo_lds[(2 * s + v) * 256], nsoff, 0);
+                }
+#endif
+                __builtin_amdgcn_sched_barrier(0);
+                if constexpr (NVB >= 1) {
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) {
+                        const int q = s * 4 + j;
+                        const v8i xb = xf[q & 1];
+                        const int xs_j = (int)xsc[q & 1];
+#pragma unroll
+                        for (int i = 0; i < NVB; ++i) {
+                            const v8i wa = wreg[slot][i];
+                            // opsel picks byte s of the lane's scale dword (compile-time after unrolling)
+                            if (s == 0) acc[i][j] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(wa, xb, acc[i][j], 0, 0, 0, (int)wsc[i], 0, xs_j);
+                            else if (s == 1) acc[i][j] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(wa, xb, acc[i][j], 0, 0, 1, (int)wsc[i], 0, xs_j);
+                            else if (s == 2) acc[i][j] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(wa, xb, acc[i][j], 0, 0, 2, (int)wsc[i], 0, xs_j);
+                            else acc[i][j] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(wa, xb, acc[i][j], 0, 0, 3, (int)wsc[i], 0, xs_j);
+                        }
+#if !(MX8_ABL & 1)
+                        if (q + 2 < STEPS * 4) read_x(q + 2, cur);       // behind the last reader of its register set
+#endif
+                        __builtin_amdgcn_sched_barrier(0);
+                    }
+                    // pin this step's MFMAs here (conv_stream_mx8_kernel: LLVM sinks them out of a multi-block step body)
+#pragma unroll
+                    for (int i = 0; i < NVB; ++i)
+#pragma unroll
+                        for (int j = 0; j < 4; ++j) asm volatile("" : "+v"(acc[i][j]));
+#if !(MX8_ABL & 2)
+#pragma unroll
+                    for (int i = 0; i < NVB; ++i) load_w(slot, i, s + D < STEPS ? wch : wnx, (s + D) & 3);
+#endif
+                }
+                __builtin_amdgcn_sched_barrier(0);
+#if !(MX8_ABL & 4)
+                if (s & 1) {
+#pragma unroll
+                    for (int v = 0; v < 4; ++v) store_vec(2 * (s - 1) + v, nxt, pq[v]);
+                }
+#endif
+                __builtin_amdgcn_sched_barrier(0);
+            }
+            if (NVB > 0) load_wsc(chunk + 1 < p.nchunks ? cl + 1 : cl);      // (behind the last chunk: unused)
+            __syncthreads();                         // next patch published; everyone is done reading the current one
+            if (NVB > 0) { read_x(0, nxt); read_x(1, nxt); }
+        }
+    };
+    const int left = ncb - (tn * 4 + wc * 2);
+    if (left >= 2) k_loop(std::integral_constant<int, 2>{});
+    else if (left == 1) k_loop(std::integral_constant<int, 1>{});
+    else k_loop(std::integral_constant<int, 0>{});
+
+    // ---- epilogue: as conv_stream_mx8_kernel, stride-2 store
+    if (p.ksplit > 1) {
+        ConvEpi e;
+        e.bias = nullptr; e.mask = nullptr; e.res = nullptr; e.y = p.ws + (size_t)split * ((size_t)p.N * p.Ho * p.Wo * p.Cout);
+        e.Cout = p.Cout; e.out_f32 = 1; e.alpha = 1.f; e.res_scale = 0.f;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int opx = out_pixel(j);
+            const bool live = opx >= 0;
+            ConvEpi ej = e;
+            if (!live) ej.Cout = 0;
+            const size_t obase = (size_t)(live ? opx : 0) * p.Cout;
+#pragma unroll
+            for (int i = 0; i < 2; ++i) conv_epilogue_block(acc[i][j], tn * 128 + wc * 64 + i * 32, lhi, obase, obase, ej);
+        }
+        return;
+    }
+    ConvEpi e;
+    e.bias = p.bias; e.mask = static_cast<const bf16_t*>(p.mask); e.res = nullptr; e.y = p.y;
+    e.Cout = p.Cout; e.out_f32 = p.out_f32; e.alpha = conv_alpha(p.alpha, p.alpha_dev); e.res_scale = 0.f;
+    e.y8 = static_cast<unsigned char*>(p.y8); e.y8_relu = p.y8_relu; e.mx_rnd = p.mx_rnd;
+    e.relu_out = p.relu_out; e.mask_bits = p.mask_bits; e.y_bits = p.y_bits;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const int pix = out_pixel(j);
+        const bool live = pix >= 0;
+        const size_t obase = (size_t)(live ? pix : 0) * p.Cout;
+        ConvEpi ej = e;
+        if (!live) ej.Cout = 0;
+        ej.y8_pix = live ? pix : 0;
+#pragma unroll
+        for (int i = 0; i < 2; ++i) conv_epilogue_block<true>(acc[i][j], tn * 128 + wc * 64 + i * 32, lhi, obase, obase, ej);
+    }
+}
+
 // y = epilogue(sum_s ws[s]) of a split-K launch (same contract as conv_splitk_finish_kernel of conv_stream.hip)
 __global__ __launch_bounds__(256) void mx8_splitk_finish_kernel(const S8Args p, long long nvec) {
     const long long v = (long long)blockIdx.x * 256 + threadIdx.x;
@@ -524,12 +766,46 @@ int mx8_ksplit(const xmc_conv_desc* d) {
     return ks < 2 ? 1 : ks;
 }
 
+// Geometry of the MX-fp8 "out" phase launch (w_packed bit 4 on the MX entry points): tiles of 256 LOW-resolution pixels, the
+// phase as a grid dimension.  The single source of truth of conv_phase_mx8_kernel's domain (xmc_conv2d_mx8_phase_supported).
+struct Mx8PhaseGeom { int wt, rt, imgs, pp, tiles_m, tiles_n, ksplit; };
+bool mx8_phase_geom(const xmc_conv_desc* d, Mx8PhaseGeom* g) {
+    if (!(d->w_packed & 1) || !((d->w_packed >> 4) & 1) || d->dtype != XMC_BF16 || d->ks != 3) return false;
+    if (!d->ups || d->pool_out) return false;        // the "in" form (pool_out) is not built
+    if (d->relu_in || d->res_ups || d->mask_after_res || d->valid_h || d->valid_w) return false;
+    if (d->n <= 0 || d->cin <= 0 || (d->cin % 64) != 0 || d->cout <= 0 || (d->cout % 32) != 0) return false;   // whole packets; the phase copies have rows % 32 == 0
+    if (d->hi < 2 || d->wi < 2 || ilog2_exact(d->hi) < 0 || ilog2_exact(d->wi) < 0) return false;
+    g->wt = d->wi < 64 ? d->wi : 64;
+    g->rt = SBM / g->wt; if (g->rt > d->hi) g->rt = d->hi;
+    g->imgs = SBM / (g->wt * g->rt);
+    g->pp = g->imgs * (g->rt + 1) * (g->wt + 1);
+    if (g->pp * 5 > NV_MAX * 256) return false;      // (2 x 2 maps: 64 images x 9 patch pixels)
+    const long long tiles_m = (long long)((d->n + g->imgs - 1) / g->imgs) * (d->wi / g->wt) * (d->hi / g->rt);
+    g->tiles_n = (d->cout + 127) / 128;
+    const long long wgs = tiles_m * g->tiles_n * 4;
+    if (wgs >= (1ll << 24)) return false;
+    g->tiles_m = (int)tiles_m;
+    const int nchunks = d->cin / 64;
+    int ks = 1;
+    if (wgs < 384 && nchunks >= 8) {                 // as the bf16 phase kernels: few-tile, long-K layers (4^2 / 8^2) only
+        ks = (int)((xmc_internal_tuning(XMC_TUNE_KSPLIT_TARGET_PHASE) + wgs / 2) / wgs);
+        if (ks > nchunks / 2) ks = nchunks / 2;
+        if (ks < 2) ks = 1;
+    }
+    g->ksplit = ks;
+    return true;
+}
+
 }  // namespace
 
-static int optin_mx8() {
+// > 64 KiB of dynamic LDS is an opt-in per kernel per device (also called by xmc_create for its device, so that a hipGraph
+// capture never meets a first-use hipFuncSetAttribute)
+extern "C" int xmc_internal_optin_mx8(void) {
     static XmcLdsOptIn opt_in;
-    return opt_in.ensure({reinterpret_cast<const void*>(&conv_stream_mx8_kernel)}, 160 * 1024) ? XMC_OK : XMC_EINVAL;
+    return opt_in.ensure({reinterpret_cast<const void*>(&conv_stream_mx8_kernel), reinterpret_cast<const void*>(&conv_phase_mx8_kernel)},
+                         160 * 1024) ? XMC_OK : XMC_EINVAL;
 }
+static int optin_mx8() { return xmc_internal_optin_mx8(); }
 
 extern "C" int xmc_mx8_quantize(const void* x, void* x8, int64_t pixels, int32_t c, int32_t relu, void* stream) {
     XMC_REQUIRE(x && x8 && pixels > 0 && c > 0 && (c % 8) == 0);
@@ -543,7 +819,7 @@ extern "C" int xmc_mx8_quantize(const void* x, void* x8, int64_t pixels, int32_t
 
 extern "C" int xmc_mx8_pack_conv_weight(const void* w_packed, void* w8, void* wscale, int32_t rows, int32_t taps, int32_t k,
                                         void* stream) {
-    XMC_REQUIRE(w_packed && w8 && wscale && rows > 0 && taps == 9 && k > 0 && (k % 32) == 0);
+    XMC_REQUIRE(w_packed && w8 && wscale && rows > 0 && (taps == 9 || taps == 16) && k > 0 && (k % 32) == 0);
     const int nrb = (rows + 31) / 32, kch32 = k / 32, nc64 = (kch32 + 1) / 2;
     const long long total = (long long)nrb * nc64 * taps * 64;
     hipLaunchKernelGGL(mx8_pack_weight_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream),
@@ -562,10 +838,64 @@ extern "C" int xmc_mx8_probe(const void* a8, const void* as, const void* b8, con
 
 extern "C" int64_t xmc_conv2d_mx8_workspace_bytes(const xmc_conv_desc* d) {
     if (!d || d->ks != 3) return 0;
-    const int ks = mx8_ksplit(d);
+    Mx8PhaseGeom g;
+    if ((d->w_packed >> 4) & 1) { if (!mx8_phase_geom(d, &g)) return 0; }
+    const int ks = ((d->w_packed >> 4) & 1) ? g.ksplit : mx8_ksplit(d);
     if (ks <= 1) return 0;
     const long long m = (long long)d->n * (d->ups ? 4 : 1) * d->hi * d->wi;
     return (int64_t)ks * m * d->cout * 4;
+}
+
+extern "C" int xmc_conv2d_mx8_phase_supported(const xmc_conv_desc* d) {
+    Mx8PhaseGeom g;
+    return d && mx8_phase_geom(d, &g) ? 1 : 0;
+}
+
+// the "out" phase form (d->w_packed bits 0 and 4, d->ups): w8 / wscale are the MX copy of the 16-tap phase weights
+static int conv2d_mx8_phase(const xmc_conv_desc* d, const void* x8, const void* w8, const void* wscale, const float* bias,
+                            const void* mask, const void* res, void* y, void* y8, int32_t y8_relu, void* ws,
+                            const void* mask_bits, void* y_bits, void* stream) {
+    Mx8PhaseGeom g;
+    if (!mx8_phase_geom(d, &g) || res) return XMC_EINVAL;
+    if ((mask_bits || y_bits) && (d->cout % 16) != 0) return XMC_EINVAL;
+    S8Args a;
+    a.x = x8; a.w = w8; a.wsc = wscale; a.bias = bias; a.mask = mask; a.res = nullptr; a.y = y;
+    a.y8 = y8; a.y8_relu = y8_relu; a.mx_rnd = xmc_mx_rnd();
+    a.relu_out = d->relu_out;
+    a.mask_bits = static_cast<const unsigned short*>(mask_bits); a.y_bits = static_cast<unsigned short*>(y_bits);
+    a.N = d->n; a.Hi = d->hi; a.Wi = d->wi; a.Cp = d->cin; a.Cout = d->cout;
+    a.Ho = 2 * d->hi; a.Wo = 2 * d->wi;
+    a.ups = 1; a.res_ups = 0; a.out_f32 = d->out_f32; a.pool_out = 0;
+    const long long m = (long long)a.N * a.Ho * a.Wo;
+    const long long xb = (long long)a.N * a.Hi * a.Wi * (a.Cp / 64) * 80;
+    const int ncb = (a.Cout + 31) / 32;
+    a.nchunks = a.Cp / 64;
+    const long long wb = (long long)ncb * a.nchunks * 16 * 2048, wsb = (long long)ncb * a.nchunks * 4 * 256;
+    if (m >= (1ll << 31) || xb >= 0xfffffff0ll || wb >= 0xfffffff0ll) return XMC_EINVAL;
+    if (((uintptr_t)x8 % 16) || ((uintptr_t)w8 % 16) || ((uintptr_t)y % 16) || ((uintptr_t)wscale % 4)) return XMC_EINVAL;
+    a.x_bytes = (unsigned)xb; a.w_bytes = (unsigned)wb; a.wsc_bytes = (unsigned)wsb;
+    a.alpha = d->alpha; a.res_scale = 0.f; a.alpha_dev = d->alpha_dev;
+    a.log2_wt = ilog2_exact(g.wt); a.log2_rt = ilog2_exact(g.rt); a.log2_imgs = ilog2_exact(g.imgs);
+    a.log2_tx = ilog2_exact(a.Wi) - a.log2_wt; a.log2_ty = ilog2_exact(a.Hi) - a.log2_rt;
+    a.PW = g.wt + 1; a.PR1 = g.rt + 1; a.PP = g.pp;
+    a.pbuf_bytes = ((a.PP + 7) & ~7) * SPITCH_B;
+    a.magic_pw = 65536 / a.PW + 1; a.magic_pr1 = 65536 / a.PR1 + 1;
+    a.tiles_m = g.tiles_m; a.tiles_n = g.tiles_n;
+    a.ksplit = ws ? g.ksplit : 1;
+    a.chunks_per_split = (a.nchunks + a.ksplit - 1) / a.ksplit;
+    a.ksplit = (a.nchunks + a.chunks_per_split - 1) / a.chunks_per_split;
+    a.ws = static_cast<float*>(ws);
+    if ((mask_bits || y_bits) && a.ksplit > 1) return XMC_EINVAL;       // the finishing pass neither reads nor writes bit masks
+    if (y8 && (a.ksplit > 1 || d->out_f32 || (a.Cout % 64) != 0 || ((uintptr_t)y8 % 16))) return XMC_EINVAL;
+    if (optin_mx8() != XMC_OK) return XMC_EINVAL;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    hipLaunchKernelGGL(conv_phase_mx8_kernel, dim3((unsigned)(a.tiles_m * a.tiles_n * a.ksplit * 4)), dim3(256),
+                       2 * (size_t)PBUF_BYTES + NV_MAX * 1024, s, a);
+    if (a.ksplit > 1) {
+        const long long nvec = m * (a.Cout / 4);
+        hipLaunchKernelGGL(mx8_splitk_finish_kernel, dim3((unsigned)((nvec + 255) / 256)), dim3(256), 0, s, a, nvec);
+    }
+    return xmc_hip_err(hipGetLastError());
 }
 
 // 3x3 convolution on MX-fp8 operands.  d->cin = true channel count (x8 rows are padded to 64), d->relu_in must be 0 (fold it
@@ -585,6 +915,8 @@ extern "C" int xmc_conv2d_mx8_bits(const xmc_conv_desc* d, const void* x8, const
                                    const float* bias, const void* mask, const void* res, void* y, void* y8, int32_t y8_relu,
                                    void* ws, const void* mask_bits, void* y_bits, void* stream) {
     XMC_REQUIRE(d && x8 && w8 && wscale && y);
+    if ((d->w_packed >> 4) & 1)                      // 16-tap phase weights: the "out" form or nothing
+        return conv2d_mx8_phase(d, x8, w8, wscale, bias, mask, res, y, y8, y8_relu, ws, mask_bits, y_bits, stream);
     if (d->ks != 3 || d->relu_in || d->mask_after_res || d->valid_h || (d->cout % 4) != 0) return XMC_EINVAL;
     if (d->pool_out && d->relu_out) return XMC_EINVAL;
     if ((mask_bits || y_bits) && (d->cout % 16) != 0) return XMC_EINVAL;

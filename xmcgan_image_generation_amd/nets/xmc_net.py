@@ -84,6 +84,9 @@ def check_config(config):
         raise ValueError("image_size must be 128 or 256 (channel_dims are only defined for those, xmc_net.py:81-86,202-205)")
     if config.get("architecture", "xmc_net") != "xmc_net":
         raise ValueError(f"Architecture {config.get('architecture')} is not supported.")
+    if config.get("conv_fp8_phase", False) and not config.get("conv_fp8", False):
+        raise ValueError("conv_fp8_phase=True needs conv_fp8=True: it moves the out-form phase launches of the MX-fp8 mode "
+                         "onto the MX-fp8 phase kernel and means nothing in the bf16 mode")
 
 
 class _Net:

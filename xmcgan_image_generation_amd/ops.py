@@ -39,7 +39,7 @@ def _p(t):
 
 class PackedWeight:
     """Prepared conv weights in MFMA-fragment order (include/xmcgan_hip.h: xmc_pack_conv_weight)."""
-    __slots__ = ("data", "cout", "taps", "cin", "mx8", "phase", "lazy")
+    __slots__ = ("data", "cout", "taps", "cin", "mx8", "phase", "lazy", "phase_mx8")
 
     def __init__(self, data, cout, taps, cin):
         self.data, self.cout, self.taps, self.cin = data, cout, taps, cin
@@ -48,6 +48,7 @@ class PackedWeight:
         self.lazy = None
         self.mx8 = None          # (w8, wscale): the MX-fp8 copy, made on first use by HipOps.conv when ops.fp8 is set
         self.phase = None        # ("out" | "in", 16-tap phase weights): xmc_phase_conv_weight, used by ups / pool_out launches
+        self.phase_mx8 = None    # (w8, wscale): the MX-fp8 twin of an "out"-kind phase copy (ops.fp8_phase_mx), made with it
 
 
 class HipOps:
@@ -86,6 +87,13 @@ class HipOps:
         # kernels it is behind -- round 5, same box, alternated (profiles/r05_c4_vs_c3.txt): C3 bf16 45.2 ms, C4 with fp8 everywhere
         # 46.8 / 47.0, C4 with the bf16 phase kernels 45.5 / 45.7 -> ON.  (Weight gradients are bf16 in either mode.)
         self.fp8_phase = os.environ.get("XMC_FP8_PHASE", "1") != "0"
+        # round 7: ... and their "out" form (ups launches: G's first block convolution, the data gradient of D's pooled convolution)
+        # on the MX-fp8 phase kernel (conv_phase_mx8_kernel: 16 block-scaled products per low-resolution pixel) -- both factors at
+        # once.  Needs fp8 and fp8_phase; the "in" form (pool_out launches) stays on the bf16 phase kernels.  Off by default
+        # (config.conv_fp8_phase; XMC_FP8_PHASE_MX=1: A/B override for bench.py --config c4)
+        self.fp8_phase_mx = os.environ.get("XMC_FP8_PHASE_MX", "0") != "0"
+        self.last_conv_mx8_phase = False      # did the last ``conv`` run on conv_phase_mx8_kernel?  (tests: no silent fallback)
+        self.mx8_phase_launches = 0           # ... and how many did since this table was made
         # race hunt: 1 = every MX convolution quantises its input itself (producer packets ignored), 2 = the
         # conditional-BatchNorm kernel writes no packets, 4 = the convolution epilogues write none
         self.fp8_debug = int(os.environ.get("XMC_FP8_DEBUG", "0"))
@@ -246,7 +254,7 @@ class HipOps:
         assert tuple(out.shape) == (n, hi, wi, w.cout) and out.dtype == self.dtype and out.is_contiguous() and x2.is_contiguous()
         assert res is None or tuple(res.shape) == tuple(out.shape)
         assert mask is None or (tuple(mask.shape) == tuple(out.shape) and mask.dtype == self.dtype)
-        self.last_conv_phase = False
+        self.last_conv_phase = self.last_conv_mx8_phase = False
         d = ConvDesc(n, hi, wi, cin, w.cout, 1, 0, 0, 0, 0, self.code, float(alpha), float(res_scale), 1 | 64 | ((getattr(self, "pw_variant", 0) & 15) << 12),
                      0, int(relu_out), int(mask_after_res), int(valid), int(valid), None)
         ybits = mbits = None
@@ -328,8 +336,13 @@ class HipOps:
                       or (pool_out and mask is None and self._phase_ok(wobj, "s2in" if stride2 else "in", hi, wi, False, True))))
         assert phase or not stride2, "stride2: see can_stride2"
         self.last_conv_phase = bool(phase)               # bench.py: this launch executes 4/9 of the 3x3 formulation's MFMAs
+        self.last_conv_mx8_phase = mx8_phase = False     # ... on conv_phase_mx8_kernel (set by _conv_mx8)
         if phase:
             w = wobj.phase[1]
+            # the "out" form on MX-fp8 operands (fp8_phase_mx): the weight carries the MX twin of its phase copy and the C side
+            # says the launch is in conv_phase_mx8_kernel's domain; anything else stays on the bf16 phase kernel, as before
+            mx8_phase = bool(self.fp8 and self.fp8_phase_mx and ups and not stride2 and not relu_out and self.dtype == torch.bfloat16
+                             and wobj.phase_mx8 is not None and self._mx8_phase_ok(hi, wi, cin, cout))
         if w is None and packed and wobj.lazy is not None:
             # a phase-only site reached by a launch outside the phase kernels' domain (a switch toggled after the weights were
             # prepared, relu_out / res / valid set, a 2 x 2 grid): make its plain 3x3 copy now, on THIS stream (a fallback: the
@@ -356,6 +369,10 @@ class HipOps:
         if res is not None:
             assert res.dtype == self.dtype
             assert tuple(res.shape) == ((n, ho // 2, wo // 2, cout) if res_ups else (n, ho, wo, cout))
+        if mx8_phase:
+            return self._conv_mx8(x, wobj, bias, y, ups=True, relu_in=relu_in, mask=mask, res=None, res_ups=False, res_scale=res_scale,
+                                  alpha=alpha, out_f32=out_f32, pool_out=False, emit=emit_mx8, alpha_dev=alpha_dev, relu_out=False,
+                                  emit_bits=emit_bits, phase=True)
         # MX-fp8 where it pays: rows are padded to 64 channels, so a 96-channel input would do 128 channels of work and its
         # (large, 128^2) tensor would pay the quantisation pass on top -- measured 0.74x the bf16 kernel; those stay bf16
         if (self.fp8 and not phase and packed and ks == 3 and self.dtype == torch.bfloat16 and not (mask_after_res or valid)
@@ -404,15 +421,30 @@ class HipOps:
         check(self.lib.xmc_mx8_quantize(_p(x), _p(x8), pixels, c, int(relu), self._stream()), "xmc_mx8_quantize")
         return x8
 
-    def pack_mx8(self, w):
-        """PackedWeight (bf16 fragment order, 9 taps) -> (w8, wscale) in the MX-fp8 fragment order of xmc_conv2d_mx8"""
-        assert isinstance(w, PackedWeight) and w.taps == 9
+    def pack_mx8(self, w, phase=False):
+        """PackedWeight (bf16 fragment order, 9 taps) -> (w8, wscale) in the MX-fp8 fragment order of xmc_conv2d_mx8;
+        ``phase``: of its 16-tap "out"-kind phase copy instead (the weights of the w_packed = 1 | 16 launch)"""
+        assert isinstance(w, PackedWeight) and w.taps == 9 and (not phase or (w.phase is not None and w.phase[0] == "out"))
+        taps = 16 if phase else 9
         nrb, nc64 = (w.cout + 31) // 32, (w.cin + 63) // 64
-        w8 = torch.empty((nrb * nc64 * 9 * 2048,), dtype=torch.uint8, device=self.device)
-        wsc = torch.zeros((nrb * nc64 * 3 * 256,), dtype=torch.uint8, device=self.device)
-        check(self.lib.xmc_mx8_pack_conv_weight(_p(w.data), _p(w8), _p(wsc), w.cout, 9, w.cin, self._stream()),
+        w8 = torch.empty((nrb * nc64 * taps * 2048,), dtype=torch.uint8, device=self.device)
+        wsc = torch.zeros((nrb * nc64 * ((taps + 3) // 4) * 256,), dtype=torch.uint8, device=self.device)
+        check(self.lib.xmc_mx8_pack_conv_weight(_p(w.phase[1] if phase else w.data), _p(w8), _p(wsc), w.cout, taps, w.cin, self._stream()),
               "xmc_mx8_pack_conv_weight")
         return w8, wsc
+
+    def _mx8_phase_ok(self, hi, wi, cin, cout):
+        """is this ``ups`` launch inside conv_phase_mx8_kernel's domain?  (the C side's own test: xmc_conv2d_mx8_phase_supported)"""
+        d = ConvDesc(1, hi, wi, cin, cout, 3, 1, 0, 0, 0, self.code, 1.0, 1.0, 1 | 16, 0, 0, 0, 0, 0)
+        return bool(self.lib.xmc_conv2d_mx8_phase_supported(C.byref(d)))
+
+    def _with_phase_mx8(self, w):
+        """MX-fp8 twin of a freshly prepared "out"-kind phase copy (``fp8_phase_mx``), made HERE, on the preparing stream, for the
+        reason ``_with_mx8`` gives: never lazily at first use"""
+        if (self.fp8 and self.fp8_phase and self.fp8_phase_mx and isinstance(w, PackedWeight) and w.phase is not None and w.phase[0] == "out"
+                and self.dtype == torch.bfloat16 and w.cin % 64 == 0 and w.cin >= self.fp8_min_cin):
+            w.phase_mx8 = self.pack_mx8(w, phase=True)
+        return w
 
     @staticmethod
     def _mx8_patch_fits(ho, wo):
@@ -437,17 +469,21 @@ class HipOps:
         return w
 
     def _conv_mx8(self, x, w, bias, y, *, ups, relu_in, mask, res, res_ups, res_scale, alpha, out_f32, pool_out, emit=None, alpha_dev=None,
-                  relu_out=False, emit_bits=False):
+                  relu_out=False, emit_bits=False, phase=False):
         n, hi, wi, cin = x.shape
-        if w.mx8 is None:                # weights prepared before ops.fp8 was set (tests, benchmarks): single-stream use only
-            w.mx8 = self.pack_mx8(w)
+        if phase:                        # the "out" phase form: the twin of the 16-tap copy (always made with it: _with_phase_mx8)
+            wmx = w.phase_mx8
+        else:
+            if w.mx8 is None:            # weights prepared before ops.fp8 was set (tests, benchmarks): single-stream use only
+                w.mx8 = self.pack_mx8(w)
+            wmx = w.mx8
         pre = getattr(x, "mx8", None)    # packets written by the producing convolution's epilogue (same relu_in)?
         if self.fp8_debug & 1:
             pre = None
         # (packets of a tensor stored AFTER its ReLU -- tag "relu" -- serve either relu_in: max(., 0) is idempotent)
         x8 = pre[0] if pre is not None and (pre[1] == "relu" or pre[1] == bool(relu_in)) else self.quantize_mx8(x, relu=relu_in)
         d = ConvDesc(n, hi, wi, cin, w.cout, 3, int(ups), 0, int(res_ups), int(out_f32), self.code, float(alpha),
-                     float(res_scale), 1, int(pool_out), int(relu_out), 0, 0, 0, alpha_dev.data_ptr() if alpha_dev is not None else None)
+                     float(res_scale), 1 | (16 if phase else 0), int(pool_out), int(relu_out), 0, 0, 0, alpha_dev.data_ptr() if alpha_dev is not None else None)
         ws_bytes = self.lib.xmc_conv2d_mx8_workspace_bytes(C.byref(d)) if not getattr(self, "no_split_k", False) else 0
         ws = self.empty((ws_bytes // 4,), torch.float32) if ws_bytes else None
         y8 = None
@@ -461,9 +497,11 @@ class HipOps:
                 mbits = mb
             if emit_bits and not out_f32:
                 ybits = torch.empty(tuple(y.shape[:-1]) + (w.cout // 16,), dtype=torch.int16, device=self.device)
-        check(self.lib.xmc_conv2d_mx8_bits(C.byref(d), _p(x8), _p(w.mx8[0]), _p(w.mx8[1]), _p(bias), _p(mask), _p(res),
+        check(self.lib.xmc_conv2d_mx8_bits(C.byref(d), _p(x8), _p(wmx[0]), _p(wmx[1]), _p(bias), _p(mask), _p(res),
                                            _p(y), _p(y8), int(bool(emit)), _p(ws), _p(mbits), _p(ybits), self._stream()),
               "xmc_conv2d_mx8_bits")
+        self.last_conv_mx8_phase = bool(phase)
+        self.mx8_phase_launches += int(bool(phase))
         if y8 is not None:
             y.mx8 = (y8, "relu" if relu_out else bool(emit))
         if ybits is not None:
@@ -579,8 +617,10 @@ class HipOps:
         check(self.lib.xmc_phase_conv_weight(_p(w), _p(inv_sigma), _p(pf16), _p(pd16), cout, cin, mode, self._stream()),
               "xmc_phase_conv_weight")
         wf.phase = (("out", "in", "s2in")[mode], pf16)
+        self._with_phase_mx8(wf)
         if pd16 is not None:
             wd.phase = (("in", "out", "s2out")[mode], pd16)
+            self._with_phase_mx8(wd)
 
     # -------------------------------------------------------------------------------------- GEMM
     def gemm(self, a, b, *, ta=False, tb=False, alpha=1.0, alpha_dev=None, beta=0.0, out=None, fast=False):
@@ -1165,6 +1205,8 @@ class HipOps:
             mode = {"ups": 0, "pool": 1}[e["phase_eff"]]
             f.phase = (("out", "in")[mode], pf_b[e["pf_off"]:e["pf_off"] + e["nph"]])
             d.phase = (("in", "out")[mode], pd_b[e["pd_off"]:e["pd_off"] + e["nph"]])
+            self._with_phase_mx8(f)
+            self._with_phase_mx8(d)
         return f, d
 
     def sn_bank_power_iter_fused(self, bank, irr, wp, params, u0_flat, part, eps=1e-10):
