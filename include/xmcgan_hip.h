@@ -38,7 +38,7 @@ extern "C" {
 #define XMC_F32 0
 #define XMC_BF16 1
 
-#define XMC_ABI_VERSION 24
+#define XMC_ABI_VERSION 25
 int xmc_abi_version(void);
 
 /* Launch-heuristic knobs -- split-K workgroup targets and tile-selection thresholds whose defaults were A/B'd inside the
@@ -178,6 +178,21 @@ int xmc_conv2d_pw_dual(const xmc_conv_desc* d, const void* x, const void* x2, in
  *   relu_in = res_ups = mask_after_res = valid_* = 0; res must be NULL.  bias, alpha, alpha_dev, mask, mask_bits, y_bits,
  *   relu_out, out_f32, y8 and the split-K workspace as for the 3x3 form (xmc_conv2d_mx8_workspace_bytes answers for these
  *   descriptors too).  Outside the domain the launch returns XMC_EINVAL; it never runs another kernel.
+ * The "in" PHASE form on MX-fp8 operands (ABI 25; entry points of their own -- on xmc_conv2d_mx8 a pool_out descriptor with bit 4
+ *   stays XMC_EINVAL): xmc_conv2d_mx8_phase_in[_bits] runs avg_pool2(conv3x3(x)) as four 2x2 convolutions on the low-resolution
+ *   OUTPUT grid, decomposed by the parity (a, b) of the input pixel: y[i][j] = 1/4 sum_{a,b} sum_{tu,tv} F_ab[tu][tv]
+ *   x[2(i+tu)-a][2(j+tv)-b] (16 instead of 36 block-scaled products per output pixel; every parity gathers whole 80-byte packets at
+ *   pixel stride 2).  d: hi / wi = the INPUT map, ups = 0, pool_out = 1, w_packed = 1 | 16; x8 = the packets of the input tensor; w8 /
+ *   wscale = the taps = 16 output of xmc_mx8_pack_conv_weight on an "in"-order phase copy (xmc_phase_conv_weight / xmc_wprep_batched:
+ *   tap = (2a + b) * 4 + tu * 2 + tv).  Replaces, when config.conv_fp8_phase_in is set, the second convolution of the down-sampling
+ *   discriminator blocks (xmcgan/nets/common.py:76-78) and the data gradient of the generator blocks' first convolution (the
+ *   adjoint of xmcgan/nets/common.py:152-159).  Domain = xmc_conv2d_mx8_phase_in_supported(d): bf16, ks = 3, pool_out, no ups,
+ *   cin % 64 == 0, cout % 32 == 0, power-of-two input maps of 8 x 8 and larger (output grids from 4 x 4), relu_in = relu_out =
+ *   res_ups = mask_after_res = valid_* = 0, no mask; the stride-2 ("s2in") copies are not its operands.  y = alpha * alpha_dev * 1/4 *
+ *   acc + bias + res_scale * res (res, y, y_bits, y8 at the output resolution); out_f32, y8 / y8_relu as xmc_conv2d_mx8; ws (may be
+ *   NULL) of xmc_conv2d_mx8_phase_in_workspace_bytes(d) bytes enables split-K (fixed-order finishing pass; then no y8 / y_bits).
+ *   Outside the domain the launch returns XMC_EINVAL; it never runs another kernel.  Measured (profiles/r08_conv_phase_in_mx_fp8.txt):
+ *   1.44 x (quantisation pass in front) / 1.82 x (on packets) the bf16 "in" phase kernel over the eight C1 launches.
  * xmc_mx8_probe: one scaled MFMA on a8 [32][64] / b8 [32][64] (B transposed) bytes with scales as / bs [32][2] ->
  *   d [32][32] float32; pins the operand layout (tests). */
 int xmc_mx8_quantize(const void* x, void* x8, int64_t pixels, int32_t c, int32_t relu, void* stream);
@@ -186,6 +201,15 @@ int xmc_mx8_pack_conv_weight(const void* w_packed, void* w8, void* wscale, int32
 int64_t xmc_conv2d_mx8_workspace_bytes(const xmc_conv_desc* d);
 /* 1 when a descriptor with w_packed bits 0 and 4 is inside the MX-fp8 "out" phase kernel's domain, else 0 */
 int xmc_conv2d_mx8_phase_supported(const xmc_conv_desc* d);
+/* 1 when the descriptor is inside the MX-fp8 "in" phase kernel's domain, else 0; its split-K workspace (0: none) */
+int xmc_conv2d_mx8_phase_in_supported(const xmc_conv_desc* d);
+int64_t xmc_conv2d_mx8_phase_in_workspace_bytes(const xmc_conv_desc* d);
+int xmc_conv2d_mx8_phase_in(const xmc_conv_desc* d, const void* x8, const void* w8, const void* wscale,
+                            const float* bias, const void* res, void* y, void* y8, int32_t y8_relu,
+                            void* ws, void* stream);
+int xmc_conv2d_mx8_phase_in_bits(const xmc_conv_desc* d, const void* x8, const void* w8, const void* wscale,
+                                 const float* bias, const void* res, void* y, void* y8, int32_t y8_relu,
+                                 void* ws, void* y_bits, void* stream);
 int xmc_conv2d_mx8(const xmc_conv_desc* d, const void* x8, const void* w8, const void* wscale,
                    const float* bias, const void* mask, const void* res, void* y, void* y8, int32_t y8_relu,
                    void* ws, void* stream);

@@ -18,7 +18,7 @@ LIB_PATH = os.path.join(_HERE, "libxmcgan_hip.so")
 PROBE_LIB_PATH = os.path.join(_HERE, "libxmc_probe.so")
 
 XMC_F32, XMC_BF16 = 0, 1
-ABI_VERSION = 24
+ABI_VERSION = 25
 
 
 class ConvDesc(C.Structure):
@@ -145,6 +145,10 @@ SIGNATURES = {
     "xmc_mx8_pack_conv_weight": [_P, _P, _P, _I, _I, _I, _P],
     "xmc_conv2d_mx8_workspace_bytes": [C.POINTER(ConvDesc)],
     "xmc_conv2d_mx8_phase_supported": [C.POINTER(ConvDesc)],
+    "xmc_conv2d_mx8_phase_in_supported": [C.POINTER(ConvDesc)],
+    "xmc_conv2d_mx8_phase_in_workspace_bytes": [C.POINTER(ConvDesc)],
+    "xmc_conv2d_mx8_phase_in": [C.POINTER(ConvDesc), _P, _P, _P, _P, _P, _P, _P, _I, _P, _P],
+    "xmc_conv2d_mx8_phase_in_bits": [C.POINTER(ConvDesc), _P, _P, _P, _P, _P, _P, _P, _I, _P, _P, _P],
     "xmc_conv2d_mx8": [C.POINTER(ConvDesc), _P, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P],
     "xmc_conv2d_mx8_bits": [C.POINTER(ConvDesc), _P, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P],
     "xmc_mx8_probe": [_P, _P, _P, _P, _P, _P],
@@ -175,7 +179,7 @@ PROBE_SIGNATURES = {
     "xmc_class_neighbour": [_I, _I, _I, _P, _L, _P, _P],
 }
 
-_INT64_RETURNS = ("xmc_conv2d_mx8_workspace_bytes", "xmc_conv2d_workspace_bytes", "xmc_bn_stats_ws_floats", "xmc_cbn_bwd_sums_ws_floats",
+_INT64_RETURNS = ("xmc_conv2d_mx8_workspace_bytes", "xmc_conv2d_mx8_phase_in_workspace_bytes", "xmc_conv2d_workspace_bytes", "xmc_bn_stats_ws_floats", "xmc_cbn_bwd_sums_ws_floats",
                   "xmc_conv2d_wgrad_workspace_bytes", "xmc_reduce_mid_ws_floats", "xmc_gemm_ws_floats")
 _lib = None
 

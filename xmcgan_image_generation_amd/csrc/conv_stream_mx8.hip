@@ -10,7 +10,8 @@
 //   weights      fragment order [cout / 32][Cp / 64][tap][piece 0..1][lane 0..63][16 bytes] + scales
 //                [cout / 32][Cp / 64][3][lane] uint32 (byte t % 4 of dword t / 4 = tap t), converted from the bf16
 //                fragment-packed copy the prep kernels already write.  The 16-tap phase copies of the layers next to a 2x
-//                upsampling convert the same way ([tap 0..15], 4 scale dwords: one per phase) for conv_phase_mx8_kernel below.
+//                resampling convert the same way ([tap 0..15], 4 scale dwords: one per phase) for conv_phase_mx8_kernel ("out" form,
+//                conv3x3(upsample2(.))) and conv_phase_in_mx8_kernel ("in" form, avg_pool2(conv3x3(.))) below.
 //
 // Operand layout of the instruction (measured: tools/mx8_probe_layout.py, pinned by tests/test_gpu_mx8.py): lane l holds
 // row / column l % 32; with h = l / 32 its registers 0..3 (16 bytes) are K = 16 h + 0..15 and its registers 4..7 are
@@ -708,6 +709,267 @@ __global__ __launch_bounds__(256, 2) void conv_phase_mx8_kernel(const S8Args p) 
     }
 }
 
+// ---- round 8: the "in" phase form on MX-fp8 operands -----------------------------------------------------------------
+// avg_pool2(conv3x3(x)) as four 2x2 convolutions on the LOW-resolution OUTPUT grid (conv_phase_kernel MODE 1 of
+// conv_stream.hip), multiplied by the block-scaled MFMA:
+//   P[i][j] = 1/4 sum_{a,b} sum_{tu,tv} F_ab[tu][tv] x[2 (i + tu) - a][2 (j + tv) - b]          (x at the HIGH resolution)
+// decomposed by the PARITY (a, b) of the input pixel: parity ph = 2a + b is a 2x2 convolution over whole 80-byte packets of the
+// sub-grid x[(2 - a) % 2 :: 2, (2 - b) % 2 :: 2] with window origin (i - a, j - b), and the four parities accumulate into the same
+// output pixel -- the phase index sits in the K loop, not in the grid.  Weights: the MX copy of the "in"-order 16-tap phase
+// weights (tap = ph * 4 + tu * 2 + tv; tap sums formed in float32, quantised once when the weight is prepared).  The kernel is
+// conv_phase_mx8_kernel with
+//   * a STAGE = one (parity, 64-channel chunk) pair = 4 K = 64 steps, walked PARITY-major like the bf16 kernel (all chunks of
+//     parity 0, then parity 1, ...): inside a parity the weight stream advances by 16 units per stage exactly as one phase's
+//     does in the "out" kernel, and consecutive stages read neighbouring packets of the same pixels;
+//   * the patch of a stage = the (Wt + 1) x (Rt + 1) packets of its parity with origin (y0 - a, x0 - b), read at pixel stride 2.
+//     The parked per-vector word (8 KiB of LDS, as before) is the byte offset of the parity-(0, 0) source pixel
+//     (2 (y0 + rr), 2 (x0 + pc)) in bits 4..31 (offsets are multiples of 16) and one validity bit per parity in bits 0..3; a
+//     stage subtracts its parity's (a Wi + b) pixels -- a scalar -- and selects "beyond the buffer" (zeros) where the bit is
+//     clear: two VALU and a select per 16-byte vector, no second offset table, LDS stays 72 KiB (two workgroups per CU);
+//   * split-K over the 64-channel chunks: every split walks its chunk range once per parity;
+//   * a plain store at the output resolution; the 1/4 of the pooling is folded into alpha by the launcher, the residual is read
+//     at the output resolution.
+// Registers / LDS as the "out" kernel: 239 VGPRs, no scratch, 72 KiB, two workgroups per CU.  Measured on one MI355X at the C1 shapes
+// (profiles/r08_conv_phase_in_mx_fp8.txt): the eight in-form launches take 1.178 ms on the bf16 "in" phase kernel, 0.818 ms here with the
+// quantisation pass in front (1.44 x) and 0.647 ms on packets (1.82 x; per row 1.60-2.03 x); with the pass in front D 64>32 (192>192) is
+// level (0.96 x).  C4 step with both phase switches 0.977 x the out-form-only C4, 0.945-0.948 x C3 (profiles/r08_c4_phase_in_mx_vs_c3.txt).
+__global__ __launch_bounds__(256, 2) void conv_phase_in_mx8_kernel(const S8Args p) {
+    constexpr int STEPS = 4;                         // taps of one parity: one K = 64 step each per 64-channel chunk
+    constexpr int D = 2;                             // weight register ring depth: slot = step % 2 (STEPS is even)
+    extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
+
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int total_tiles = p.tiles_m * p.tiles_n;
+    const int wid = xcd_remap(blockIdx.x, total_tiles * p.ksplit);
+    const int split = wid / total_tiles, tile = wid - split * total_tiles;
+    const int tn = tile / p.tiles_m, tm = tile - tn * p.tiles_m;
+    const int c_begin = split * p.chunks_per_split;
+    const int c_end = min(p.nchunks, c_begin + p.chunks_per_split);
+    const int Wt = 1 << p.log2_wt, Rt = 1 << p.log2_rt;
+    const int tx = tm & ((1 << p.log2_tx) - 1), rest = tm >> p.log2_tx;
+    const int ty = rest & ((1 << p.log2_ty) - 1);
+    const int img0 = (rest >> p.log2_ty) << p.log2_imgs;
+    const int y0 = ty << p.log2_rt, x0 = tx << p.log2_wt;        // origin of the tile on the OUTPUT (low-resolution) grid
+
+    const __amdgpu_buffer_rsrc_t xr = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p.x), 0, p.x_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t wr = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p.w), 0, p.w_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t wsr = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p.wsc), 0, p.wsc_bytes, 0x00020000);
+    constexpr unsigned OOB = 0xfffffff0u;            // beyond any buffer: the load returns zeros
+
+    // ---- patch staging: vector v = thread + 256 i is vector v % 5 of patch pixel v / 5 (conv_stream_mx8_kernel).  Patch pixel
+    //      (rr, pc) of parity (a, b) is input pixel (2 (y0 + rr) - a, 2 (x0 + pc) - b): inside the map iff y0 + rr < Ho (a = 0) /
+    //      y0 + rr >= 1 (a = 1), the same for the columns (y0 + rr runs over 0 .. Ho inclusive).
+    const int nvec = p.PP * 5;
+    const int row_bytes = (p.Cp >> 6) * 80;          // one pixel of x8
+    auto patch_word = [&](int i) -> unsigned {
+        const int v = tid + 256 * i;
+        const int pp = (v * 13108) >> 16, kv = v - pp * 5;               // v / 5 for v < 2^14
+        const int pr = (pp * p.magic_pw) >> 16, pc = pp - pr * p.PW;
+        const int im = (pr * p.magic_pr1) >> 16, rr = pr - im * p.PR1;
+        const int yv = y0 + rr, xv = x0 + pc;
+        const unsigned live = (v < nvec) & (img0 + im < p.N);
+        const unsigned ry0 = live & (yv < p.Ho), ry1 = live & (yv >= 1), cx0 = xv < p.Wo, cx1 = xv >= 1;
+        const unsigned m = (ry0 & cx0) | ((ry0 & cx1) << 1) | ((ry1 & cx0) << 2) | ((ry1 & cx1) << 3);
+        return ((unsigned)(((img0 + im) * p.Hi + 2 * yv) * p.Wi + 2 * xv) * (unsigned)row_bytes + (unsigned)(kv * 16)) | m;
+    };
+    // this stage's parity: the pixels to step back from the parity-(0, 0) source (a scalar)
+    auto parity_delta = [&](int ph) -> unsigned { return (unsigned)(((ph >> 1) * p.Wi + (ph & 1)) * row_bytes); };
+    auto patch_voff = [&](unsigned word, unsigned bit, unsigned delta) -> unsigned {
+        return (word & bit) ? (word & ~15u) - delta : OOB;
+    };
+    unsigned* const pvo_lds = reinterpret_cast<unsigned*>(lds + 2 * PBUF_BYTES) + tid;     // + i * 256
+    auto store_vec = [&](int i, int bufoff, u32x4 q) {
+        *reinterpret_cast<u32x4*>(lds + bufoff + (tid + 256 * i) * 16) = q;
+    };
+
+    // ---- MFMA geometry: wave -> 64 cout x 128 output pixels (2 x 4 blocks)
+    const int wp = wave >> 1, wc = (wave ^ (blockIdx.x >> 3)) & 1;
+    const int l31 = lane & 31, lhi = lane >> 5;
+    int pbase[4];                                    // LDS byte offset of (lane's pixel, tap (0,0), channels 16 lhi ..) in buffer 0
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const int t = wp * 128 + j * 32 + l31;
+        const int c = t & (Wt - 1), rowi = t >> p.log2_wt;
+        const int im = rowi >> p.log2_rt, rj = rowi & (Rt - 1);
+        pbase[j] = ((im * p.PR1 + rj) * p.PW + c) * SPITCH_B + lhi * 16;
+    }
+    auto out_pixel = [&](int j) {                    // output pixel index of block j's lane (or -1); epilogue only
+        const int t = wp * 128 + j * 32 + l31;
+        const int c = t & (Wt - 1), rowi = t >> p.log2_wt;
+        const int im = rowi >> p.log2_rt, rj = rowi & (Rt - 1);
+        return (img0 + im < p.N) ? ((img0 + im) * p.Ho + y0 + rj) * p.Wo + x0 + c : -1;
+    };
+    const int soff = 64 - 15 * lhi;                  // scale byte of K block lhi (row byte 64 + lhi), relative to pbase
+    // ---- weight stream: block cb = tn * 4 + wc * 2 + i; a chunk holds 16 units (4 parities x 4 taps): stage (ph, c) starts at
+    //      unit c * 16 + ph * 4 of the block, its scale dword is number c * 4 + ph
+    const int ncb = (p.Cout + 31) >> 5;
+    unsigned wvoff[2], wsvoff[2];
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+        const int cb = tn * 4 + wc * 2 + i;
+        wvoff[i] = cb < ncb ? (unsigned)(cb * p.nchunks) * 32768u + lane * 16 : OOB;
+        wsvoff[i] = cb < ncb ? (unsigned)(cb * p.nchunks) * 1024u + lane * 4 : OOB;
+    }
+    v8i wreg[D][2];
+    auto load_w = [&](int slot, int i, int wst, int u) {             // unit u = tap u of the stage at byte wst
+        const int off = wst + u * 2048;
+        wreg[slot][i] = join8(__builtin_amdgcn_raw_buffer_load_b128(wr, wvoff[i], off, 0),
+                              __builtin_amdgcn_raw_buffer_load_b128(wr, wvoff[i], off + 1024, 0));
+    };
+    unsigned wsc[2];                                 // this stage's weight scales: byte s = tap s of its parity
+    auto load_wsc = [&](int ph, int chunk) {
+#pragma unroll
+        for (int i = 0; i < 2; ++i) wsc[i] = __builtin_amdgcn_raw_buffer_load_b32(wsr, wsvoff[i], (chunk * 4 + ph) * 256, 0);
+    };
+
+    f32x16 acc[2][4];
+    v8i xf[2];                                       // B fragments: q = tap * 4 + j in xf[q & 1], read two fragments ahead
+    unsigned xsc[2];
+    auto read_x = [&](int q, int bufoff) {
+        const int tap = q >> 2, j = q & 3;
+        const int off = bufoff + ((tap >> 1) * p.PW + (tap & 1)) * SPITCH_B;
+        xf[q & 1] = join8(*reinterpret_cast<const u32x4*>(lds + pbase[j] + off), *reinterpret_cast<const u32x4*>(lds + pbase[j] + off + 32));
+        xsc[q & 1] = lds[pbase[j] + off + soff];
+    };
+
+    // ---- prologue: whole patch of stage (parity 0, chunk c_begin) -> buffer 0; weight units 0 .. D-1; its scales
+    {
+        u32x4 p0[NV_MAX];
+#pragma unroll
+        for (int i = 0; i < NV_MAX; ++i) {
+            const unsigned word = patch_word(i);
+            pvo_lds[i * 256] = word;                 // read back only by this thread: no barrier needed for it
+            p0[i] = __builtin_amdgcn_raw_buffer_load_b128(xr, patch_voff(word, 1u, 0u), c_begin * 80, 0);
+        }
+#pragma unroll
+        for (int u = 0; u < D; ++u)
+#pragma unroll
+            for (int i = 0; i < 2; ++i) load_w(u, i, c_begin * 32768, u);
+        load_wsc(0, c_begin);
+#pragma unroll
+        for (int i = 0; i < NV_MAX; ++i) store_vec(i, 0, p0[i]);
+    }
+    __syncthreads();
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+#pragma unroll
+            for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
+    read_x(0, 0); read_x(1, 0);
+
+    auto k_loop = [&](auto nv_tag) {
+        constexpr int NVB = decltype(nv_tag)::value;
+        const int nst = (c_end - c_begin) * 4;
+        int ph = 0, chunk = c_begin;
+        for (int st = 0; st < nst; ++st) {
+            const bool next = st + 1 < nst;
+            int nph = ph, nchunk = chunk + 1;        // the stage after this one (behind the last: this one again, unused)
+            if (nchunk == c_end) { nchunk = c_begin; nph = ph + 1; }
+            if (!next) { nchunk = chunk; nph = ph; }
+            const int cur = (st & 1) * PBUF_BYTES, nxt = PBUF_BYTES - cur;
+            const unsigned nbit = next ? 1u << nph : 0u;                 // (last stage: every vector beyond the buffer, no traffic)
+            const unsigned ndelta = parity_delta(nph);
+            const int nsoff = nchunk * 80;
+            const int wst = (chunk * 16 + ph * 4) * 2048, wnx = (nchunk * 16 + nph * 4) * 2048;
+            u32x4 pq[4];
+#pragma unroll
+            for (int s = 0; s < STEPS; ++s) {
+                const int slot = s & 1;
+#if !(MX8_ABL & 4)
+                if ((s & 1) == 0) {
+#pragma unroll
+                    for (int v = 0; v < 4; ++v)
+                        pq[v] = __builtin_amdgcn_raw_buffer_load_b128(xr, patch_voff(pvo_lds[(2 * s + v) * 256], nbit, ndelta), nsoff, 0);
+                }
+#endif
+                __builtin_amdgcn_sched_barrier(0);
+                if constexpr (NVB >= 1) {
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) {
+                        const int q = s * 4 + j;
+                        const v8i xb = xf[q & 1];
+                        const int xs_j = (int)xsc[q & 1];
+#pragma unroll
+                        for (int i = 0; i < NVB; ++i) {
+                            const v8i wa = wreg[slot][i];
+                            // opsel picks byte s of the lane's scale dword (compile-time after unrolling)
+                            if (s == 0) acc[i][j] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(wa, xb, acc[i][j], 0, 0, 0, (int)wsc[i], 0, xs_j);
+                            else if (s == 1) acc[i][j] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(wa, xb, acc[i][j], 0, 0, 1, (int)wsc[i], 0, xs_j);
+                            else if (s == 2) acc[i][j] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(wa, xb, acc[i][j], 0, 0, 2, (int)wsc[i], 0, xs_j);
+                            else acc[i][j] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(wa, xb, acc[i][j], 0, 0, 3, (int)wsc[i], 0, xs_j);
+                        }
+#if !(MX8_ABL & 1)
+                        if (q + 2 < STEPS * 4) read_x(q + 2, cur);       // behind the last reader of its register set
+#endif
+                        __builtin_amdgcn_sched_barrier(0);
+                    }
+                    // pin this step's MFMAs here (conv_stream_mx8_kernel: LLVM sinks them out of a multi-block step body)
+#pragma unroll
+                    for (int i = 0; i < NVB; ++i)
+#pragma unroll
+                        for (int j = 0; j < 4; ++j) asm volatile("" : "+v"(acc[i][j]));
+#if !(MX8_ABL & 2)
+#pragma unroll
+                    for (int i = 0; i < NVB; ++i) load_w(slot, i, s + D < STEPS ? wst : wnx, (s + D) & 3);
+#endif
+                }
+                __builtin_amdgcn_sched_barrier(0);
+#if !(MX8_ABL & 4)
+                if (s & 1) {
+#pragma unroll
+                    for (int v = 0; v < 4; ++v) store_vec(2 * (s - 1) + v, nxt, pq[v]);
+                }
+#endif
+                __builtin_amdgcn_sched_barrier(0);
+            }
+            if (NVB > 0) load_wsc(nph, nchunk);
+            __syncthreads();                         // next patch published; everyone is done reading the current one
+            if (NVB > 0) { read_x(0, nxt); read_x(1, nxt); }
+            ph = nph; chunk = nchunk;
+        }
+    };
+    const int left = ncb - (tn * 4 + wc * 2);
+    if (left >= 2) k_loop(std::integral_constant<int, 2>{});
+    else if (left == 1) k_loop(std::integral_constant<int, 1>{});
+    else k_loop(std::integral_constant<int, 0>{});
+
+    // ---- epilogue: as conv_stream_mx8_kernel without pooling (the accumulators ARE the pooled sums; p.alpha carries the 1/4)
+    if (p.ksplit > 1) {
+        ConvEpi e;
+        e.bias = nullptr; e.mask = nullptr; e.res = nullptr; e.y = p.ws + (size_t)split * ((size_t)p.N * p.Ho * p.Wo * p.Cout);
+        e.Cout = p.Cout; e.out_f32 = 1; e.alpha = 1.f; e.res_scale = 0.f;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int opx = out_pixel(j);
+            const bool live = opx >= 0;
+            ConvEpi ej = e;
+            if (!live) ej.Cout = 0;
+            const size_t obase = (size_t)(live ? opx : 0) * p.Cout;
+#pragma unroll
+            for (int i = 0; i < 2; ++i) conv_epilogue_block(acc[i][j], tn * 128 + wc * 64 + i * 32, lhi, obase, obase, ej);
+        }
+        return;
+    }
+    ConvEpi e;
+    e.bias = p.bias; e.mask = nullptr; e.res = static_cast<const bf16_t*>(p.res); e.y = p.y;
+    e.Cout = p.Cout; e.out_f32 = p.out_f32; e.alpha = conv_alpha(p.alpha, p.alpha_dev); e.res_scale = p.res_scale;
+    e.y8 = static_cast<unsigned char*>(p.y8); e.y8_relu = p.y8_relu; e.mx_rnd = p.mx_rnd;
+    e.relu_out = 0; e.mask_bits = nullptr; e.y_bits = p.y_bits;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const int pix = out_pixel(j);
+        const bool live = pix >= 0;
+        const size_t obase = (size_t)(live ? pix : 0) * p.Cout;
+        ConvEpi ej = e;
+        if (!live) ej.Cout = 0;
+        ej.y8_pix = live ? pix : 0;
+#pragma unroll
+        for (int i = 0; i < 2; ++i) conv_epilogue_block<true>(acc[i][j], tn * 128 + wc * 64 + i * 32, lhi, obase, obase, ej);
+    }
+}
+
 // y = epilogue(sum_s ws[s]) of a split-K launch (same contract as conv_splitk_finish_kernel of conv_stream.hip)
 __global__ __launch_bounds__(256) void mx8_splitk_finish_kernel(const S8Args p, long long nvec) {
     const long long v = (long long)blockIdx.x * 256 + threadIdx.x;
@@ -796,13 +1058,44 @@ bool mx8_phase_geom(const xmc_conv_desc* d, Mx8PhaseGeom* g) {
     return true;
 }
 
+// Geometry of the MX-fp8 "in" phase launch (xmc_conv2d_mx8_phase_in*): tiles of 256 OUTPUT (low-resolution) pixels, the input
+// parity in the K loop.  The single source of truth of conv_phase_in_mx8_kernel's domain (xmc_conv2d_mx8_phase_in_supported).
+bool mx8_phase_in_geom(const xmc_conv_desc* d, Mx8PhaseGeom* g) {
+    if (!(d->w_packed & 1) || !((d->w_packed >> 4) & 1) || d->dtype != XMC_BF16 || d->ks != 3) return false;
+    if (d->ups || !d->pool_out) return false;        // the "out" form is xmc_conv2d_mx8 with ups
+    if (d->relu_in || d->relu_out || d->res_ups || d->mask_after_res || d->valid_h || d->valid_w) return false;
+    if (d->n <= 0 || d->cin <= 0 || (d->cin % 64) != 0 || d->cout <= 0 || (d->cout % 32) != 0) return false;   // whole packets; the phase copies have rows % 32 == 0
+    if (d->hi < 8 || d->wi < 8 || ilog2_exact(d->hi) < 0 || ilog2_exact(d->wi) < 0) return false;             // output grids from 4 x 4
+    const int ho = d->hi / 2, wo = d->wi / 2;
+    g->wt = wo < 64 ? wo : 64;
+    g->rt = SBM / g->wt; if (g->rt > ho) g->rt = ho;
+    g->imgs = SBM / (g->wt * g->rt);
+    g->pp = g->imgs * (g->rt + 1) * (g->wt + 1);
+    if (g->pp * 5 > NV_MAX * 256) return false;
+    const long long tiles_m = (long long)((d->n + g->imgs - 1) / g->imgs) * (wo / g->wt) * (ho / g->rt);
+    g->tiles_n = (d->cout + 127) / 128;
+    const long long wgs = tiles_m * g->tiles_n;
+    if (wgs >= (1ll << 24)) return false;
+    g->tiles_m = (int)tiles_m;
+    const int nchunks = d->cin / 64;
+    int ks = 1;
+    if (wgs < 384 && nchunks >= 8) {                 // as the bf16 phase kernels: few-tile, long-K layers (4^2 / 8^2) only
+        ks = (int)((xmc_internal_tuning(XMC_TUNE_KSPLIT_TARGET_PHASE) + wgs / 2) / wgs);
+        if (ks > nchunks / 2) ks = nchunks / 2;
+        if (ks < 2) ks = 1;
+    }
+    g->ksplit = ks;
+    return true;
+}
+
 }  // namespace
 
 // > 64 KiB of dynamic LDS is an opt-in per kernel per device (also called by xmc_create for its device, so that a hipGraph
 // capture never meets a first-use hipFuncSetAttribute)
 extern "C" int xmc_internal_optin_mx8(void) {
     static XmcLdsOptIn opt_in;
-    return opt_in.ensure({reinterpret_cast<const void*>(&conv_stream_mx8_kernel), reinterpret_cast<const void*>(&conv_phase_mx8_kernel)},
+    return opt_in.ensure({reinterpret_cast<const void*>(&conv_stream_mx8_kernel), reinterpret_cast<const void*>(&conv_phase_mx8_kernel),
+                          reinterpret_cast<const void*>(&conv_phase_in_mx8_kernel)},
                          160 * 1024) ? XMC_OK : XMC_EINVAL;
 }
 static int optin_mx8() { return xmc_internal_optin_mx8(); }
@@ -896,6 +1189,72 @@ static int conv2d_mx8_phase(const xmc_conv_desc* d, const void* x8, const void* 
         hipLaunchKernelGGL(mx8_splitk_finish_kernel, dim3((unsigned)((nvec + 255) / 256)), dim3(256), 0, s, a, nvec);
     }
     return xmc_hip_err(hipGetLastError());
+}
+
+// ---- the "in" phase form: avg_pool2(conv3x3(x)) on conv_phase_in_mx8_kernel.  d: hi / wi = the INPUT (high-resolution) map,
+// pool_out = 1, ups = 0, w_packed = 1 | 16; w8 / wscale = the MX copy (taps = 16) of the "in"-order 16-tap phase weights; res
+// and y at the output resolution.  Entry points of their own: on xmc_conv2d_mx8 the same descriptor stays XMC_EINVAL.
+extern "C" int xmc_conv2d_mx8_phase_in_supported(const xmc_conv_desc* d) {
+    Mx8PhaseGeom g;
+    return d && mx8_phase_in_geom(d, &g) ? 1 : 0;
+}
+
+extern "C" int64_t xmc_conv2d_mx8_phase_in_workspace_bytes(const xmc_conv_desc* d) {
+    Mx8PhaseGeom g;
+    if (!d || !mx8_phase_in_geom(d, &g) || g.ksplit <= 1) return 0;
+    return (int64_t)g.ksplit * ((long long)d->n * (d->hi / 2) * (d->wi / 2)) * d->cout * 4;
+}
+
+extern "C" int xmc_conv2d_mx8_phase_in_bits(const xmc_conv_desc* d, const void* x8, const void* w8, const void* wscale,
+                                            const float* bias, const void* res, void* y, void* y8, int32_t y8_relu,
+                                            void* ws, void* y_bits, void* stream) {
+    XMC_REQUIRE(d && x8 && w8 && wscale && y);
+    Mx8PhaseGeom g;
+    if (!mx8_phase_in_geom(d, &g)) return XMC_EINVAL;
+    if (y_bits && (d->cout % 16) != 0) return XMC_EINVAL;
+    S8Args a;
+    a.x = x8; a.w = w8; a.wsc = wscale; a.bias = bias; a.mask = nullptr; a.res = res; a.y = y;
+    a.y8 = y8; a.y8_relu = y8_relu; a.mx_rnd = xmc_mx_rnd();
+    a.relu_out = 0; a.mask_bits = nullptr; a.y_bits = static_cast<unsigned short*>(y_bits);
+    a.N = d->n; a.Hi = d->hi; a.Wi = d->wi; a.Cp = d->cin; a.Cout = d->cout;
+    a.Ho = d->hi / 2; a.Wo = d->wi / 2;
+    a.ups = 0; a.res_ups = 0; a.out_f32 = d->out_f32; a.pool_out = 0;      // (the finishing pass sees a plain launch on Ho x Wo)
+    const long long m = (long long)a.N * a.Ho * a.Wo;
+    const long long xb = 4 * m * (a.Cp / 64) * 80;
+    const int ncb = (a.Cout + 31) / 32;
+    a.nchunks = a.Cp / 64;
+    const long long wb = (long long)ncb * a.nchunks * 16 * 2048, wsb = (long long)ncb * a.nchunks * 4 * 256;
+    if (4 * m >= (1ll << 31) || xb >= 0xfffffff0ll || wb >= 0xfffffff0ll) return XMC_EINVAL;
+    if (((uintptr_t)x8 % 16) || ((uintptr_t)w8 % 16) || ((uintptr_t)y % 16) || ((uintptr_t)wscale % 4)) return XMC_EINVAL;
+    a.x_bytes = (unsigned)xb; a.w_bytes = (unsigned)wb; a.wsc_bytes = (unsigned)wsb;
+    a.alpha = 0.25f * d->alpha; a.res_scale = d->res_scale; a.alpha_dev = d->alpha_dev;      // the 1/4 of the average pooling
+    a.log2_wt = ilog2_exact(g.wt); a.log2_rt = ilog2_exact(g.rt); a.log2_imgs = ilog2_exact(g.imgs);
+    a.log2_tx = ilog2_exact(a.Wo) - a.log2_wt; a.log2_ty = ilog2_exact(a.Ho) - a.log2_rt;
+    a.PW = g.wt + 1; a.PR1 = g.rt + 1; a.PP = g.pp;
+    a.pbuf_bytes = ((a.PP + 7) & ~7) * SPITCH_B;
+    a.magic_pw = 65536 / a.PW + 1; a.magic_pr1 = 65536 / a.PR1 + 1;
+    a.tiles_m = g.tiles_m; a.tiles_n = g.tiles_n;
+    a.ksplit = ws ? g.ksplit : 1;
+    a.chunks_per_split = (a.nchunks + a.ksplit - 1) / a.ksplit;
+    a.ksplit = (a.nchunks + a.chunks_per_split - 1) / a.chunks_per_split;
+    a.ws = static_cast<float*>(ws);
+    if (y_bits && a.ksplit > 1) return XMC_EINVAL;                       // the finishing pass writes no bit masks
+    if (y8 && (a.ksplit > 1 || d->out_f32 || (a.Cout % 64) != 0 || ((uintptr_t)y8 % 16))) return XMC_EINVAL;
+    if (optin_mx8() != XMC_OK) return XMC_EINVAL;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    hipLaunchKernelGGL(conv_phase_in_mx8_kernel, dim3((unsigned)(a.tiles_m * a.tiles_n * a.ksplit)), dim3(256),
+                       2 * (size_t)PBUF_BYTES + NV_MAX * 1024, s, a);
+    if (a.ksplit > 1) {
+        const long long nvec = m * (a.Cout / 4);
+        hipLaunchKernelGGL(mx8_splitk_finish_kernel, dim3((unsigned)((nvec + 255) / 256)), dim3(256), 0, s, a, nvec);
+    }
+    return xmc_hip_err(hipGetLastError());
+}
+
+extern "C" int xmc_conv2d_mx8_phase_in(const xmc_conv_desc* d, const void* x8, const void* w8, const void* wscale,
+                                       const float* bias, const void* res, void* y, void* y8, int32_t y8_relu,
+                                       void* ws, void* stream) {
+    return xmc_conv2d_mx8_phase_in_bits(d, x8, w8, wscale, bias, res, y, y8, y8_relu, ws, nullptr, stream);
 }
 
 // 3x3 convolution on MX-fp8 operands.  d->cin = true channel count (x8 rows are padded to 64), d->relu_in must be 0 (fold it

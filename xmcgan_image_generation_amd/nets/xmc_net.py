@@ -87,6 +87,9 @@ def check_config(config):
     if config.get("conv_fp8_phase", False) and not config.get("conv_fp8", False):
         raise ValueError("conv_fp8_phase=True needs conv_fp8=True: it moves the out-form phase launches of the MX-fp8 mode "
                          "onto the MX-fp8 phase kernel and means nothing in the bf16 mode")
+    if config.get("conv_fp8_phase_in", False) and not config.get("conv_fp8", False):
+        raise ValueError("conv_fp8_phase_in=True needs conv_fp8=True: it moves the in-form phase launches of the MX-fp8 mode "
+                         "onto the MX-fp8 \"in\" phase kernel and means nothing in the bf16 mode")
 
 
 class _Net:

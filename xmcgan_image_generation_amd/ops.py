@@ -48,7 +48,8 @@ class PackedWeight:
         self.lazy = None
         self.mx8 = None          # (w8, wscale): the MX-fp8 copy, made on first use by HipOps.conv when ops.fp8 is set
         self.phase = None        # ("out" | "in", 16-tap phase weights): xmc_phase_conv_weight, used by ups / pool_out launches
-        self.phase_mx8 = None    # (w8, wscale): the MX-fp8 twin of an "out"-kind phase copy (ops.fp8_phase_mx), made with it
+        self.phase_mx8 = None    # (w8, wscale): the MX-fp8 twin of the phase copy, made with it -- of an "out"-kind copy under
+                                 # ops.fp8_phase_mx, of an "in"-kind copy under ops.fp8_phase_in_mx
 
 
 class HipOps:
@@ -89,11 +90,18 @@ class HipOps:
         self.fp8_phase = os.environ.get("XMC_FP8_PHASE", "1") != "0"
         # round 7: ... and their "out" form (ups launches: G's first block convolution, the data gradient of D's pooled convolution)
         # on the MX-fp8 phase kernel (conv_phase_mx8_kernel: 16 block-scaled products per low-resolution pixel) -- both factors at
-        # once.  Needs fp8 and fp8_phase; the "in" form (pool_out launches) stays on the bf16 phase kernels.  Off by default
+        # once.  Needs fp8 and fp8_phase; the "in" form (pool_out launches) stays on the bf16 phase kernels unless fp8_phase_in_mx (below).  Off by default
         # (config.conv_fp8_phase; XMC_FP8_PHASE_MX=1: A/B override for bench.py --config c4)
         self.fp8_phase_mx = os.environ.get("XMC_FP8_PHASE_MX", "0") != "0"
         self.last_conv_mx8_phase = False      # did the last ``conv`` run on conv_phase_mx8_kernel?  (tests: no silent fallback)
         self.mx8_phase_launches = 0           # ... and how many did since this table was made
+        # round 8: ... and their "in" form (pool_out launches: the second convolution of D's down-sampling blocks, the data gradient
+        # of G's first block convolution) on conv_phase_in_mx8_kernel -- the input parity in the K loop, whole packets at pixel
+        # stride 2.  A switch of its own (either, both or neither): needs fp8 and fp8_phase.  Off by default
+        # (config.conv_fp8_phase_in; XMC_FP8_PHASE_IN_MX=1: A/B override for bench.py --config c4)
+        self.fp8_phase_in_mx = os.environ.get("XMC_FP8_PHASE_IN_MX", "0") != "0"
+        self.last_conv_mx8_phase_in = False   # did the last ``conv`` run on conv_phase_in_mx8_kernel?  (tests: no silent fallback)
+        self.mx8_phase_in_launches = 0        # ... and how many did since this table was made
         # race hunt: 1 = every MX convolution quantises its input itself (producer packets ignored), 2 = the
         # conditional-BatchNorm kernel writes no packets, 4 = the convolution epilogues write none
         self.fp8_debug = int(os.environ.get("XMC_FP8_DEBUG", "0"))
@@ -254,7 +262,7 @@ class HipOps:
         assert tuple(out.shape) == (n, hi, wi, w.cout) and out.dtype == self.dtype and out.is_contiguous() and x2.is_contiguous()
         assert res is None or tuple(res.shape) == tuple(out.shape)
         assert mask is None or (tuple(mask.shape) == tuple(out.shape) and mask.dtype == self.dtype)
-        self.last_conv_phase = self.last_conv_mx8_phase = False
+        self.last_conv_phase = self.last_conv_mx8_phase = self.last_conv_mx8_phase_in = False
         d = ConvDesc(n, hi, wi, cin, w.cout, 1, 0, 0, 0, 0, self.code, float(alpha), float(res_scale), 1 | 64 | ((getattr(self, "pw_variant", 0) & 15) << 12),
                      0, int(relu_out), int(mask_after_res), int(valid), int(valid), None)
         ybits = mbits = None
@@ -337,12 +345,16 @@ class HipOps:
         assert phase or not stride2, "stride2: see can_stride2"
         self.last_conv_phase = bool(phase)               # bench.py: this launch executes 4/9 of the 3x3 formulation's MFMAs
         self.last_conv_mx8_phase = mx8_phase = False     # ... on conv_phase_mx8_kernel (set by _conv_mx8)
+        self.last_conv_mx8_phase_in = mx8_phase_in = False   # ... on conv_phase_in_mx8_kernel (set by _conv_mx8)
         if phase:
             w = wobj.phase[1]
             # the "out" form on MX-fp8 operands (fp8_phase_mx): the weight carries the MX twin of its phase copy and the C side
             # says the launch is in conv_phase_mx8_kernel's domain; anything else stays on the bf16 phase kernel, as before
             mx8_phase = bool(self.fp8 and self.fp8_phase_mx and ups and not stride2 and not relu_out and self.dtype == torch.bfloat16
                              and wobj.phase_mx8 is not None and self._mx8_phase_ok(hi, wi, cin, cout))
+            # ... and the "in" form (fp8_phase_in_mx) likewise on conv_phase_in_mx8_kernel
+            mx8_phase_in = bool(self.fp8 and self.fp8_phase_in_mx and pool_out and not stride2 and not relu_out and self.dtype == torch.bfloat16
+                                and wobj.phase[0] == "in" and wobj.phase_mx8 is not None and self._mx8_phase_in_ok(hi, wi, cin, cout))
         if w is None and packed and wobj.lazy is not None:
             # a phase-only site reached by a launch outside the phase kernels' domain (a switch toggled after the weights were
             # prepared, relu_out / res / valid set, a 2 x 2 grid): make its plain 3x3 copy now, on THIS stream (a fallback: the
@@ -373,6 +385,10 @@ class HipOps:
             return self._conv_mx8(x, wobj, bias, y, ups=True, relu_in=relu_in, mask=mask, res=None, res_ups=False, res_scale=res_scale,
                                   alpha=alpha, out_f32=out_f32, pool_out=False, emit=emit_mx8, alpha_dev=alpha_dev, relu_out=False,
                                   emit_bits=emit_bits, phase=True)
+        if mx8_phase_in:
+            return self._conv_mx8(x, wobj, bias, y, ups=False, relu_in=relu_in, mask=None, res=res, res_ups=False, res_scale=res_scale,
+                                  alpha=alpha, out_f32=out_f32, pool_out=True, emit=emit_mx8, alpha_dev=alpha_dev, relu_out=False,
+                                  emit_bits=emit_bits, phase="in")
         # MX-fp8 where it pays: rows are padded to 64 channels, so a 96-channel input would do 128 channels of work and its
         # (large, 128^2) tensor would pay the quantisation pass on top -- measured 0.74x the bf16 kernel; those stay bf16
         if (self.fp8 and not phase and packed and ks == 3 and self.dtype == torch.bfloat16 and not (mask_after_res or valid)
@@ -423,8 +439,8 @@ class HipOps:
 
     def pack_mx8(self, w, phase=False):
         """PackedWeight (bf16 fragment order, 9 taps) -> (w8, wscale) in the MX-fp8 fragment order of xmc_conv2d_mx8;
-        ``phase``: of its 16-tap "out"-kind phase copy instead (the weights of the w_packed = 1 | 16 launch)"""
-        assert isinstance(w, PackedWeight) and w.taps == 9 and (not phase or (w.phase is not None and w.phase[0] == "out"))
+        ``phase``: of its 16-tap "out"- or "in"-kind phase copy instead (the weights of the w_packed = 1 | 16 launches)"""
+        assert isinstance(w, PackedWeight) and w.taps == 9 and (not phase or (w.phase is not None and w.phase[0] in ("out", "in")))
         taps = 16 if phase else 9
         nrb, nc64 = (w.cout + 31) // 32, (w.cin + 63) // 64
         w8 = torch.empty((nrb * nc64 * taps * 2048,), dtype=torch.uint8, device=self.device)
@@ -438,10 +454,16 @@ class HipOps:
         d = ConvDesc(1, hi, wi, cin, cout, 3, 1, 0, 0, 0, self.code, 1.0, 1.0, 1 | 16, 0, 0, 0, 0, 0)
         return bool(self.lib.xmc_conv2d_mx8_phase_supported(C.byref(d)))
 
+    def _mx8_phase_in_ok(self, hi, wi, cin, cout):
+        """is this ``pool_out`` launch inside conv_phase_in_mx8_kernel's domain?  (the C side's own test: xmc_conv2d_mx8_phase_in_supported)"""
+        d = ConvDesc(1, hi, wi, cin, cout, 3, 0, 0, 0, 0, self.code, 1.0, 1.0, 1 | 16, 1, 0, 0, 0, 0)
+        return bool(self.lib.xmc_conv2d_mx8_phase_in_supported(C.byref(d)))
+
     def _with_phase_mx8(self, w):
-        """MX-fp8 twin of a freshly prepared "out"-kind phase copy (``fp8_phase_mx``), made HERE, on the preparing stream, for the
-        reason ``_with_mx8`` gives: never lazily at first use"""
-        if (self.fp8 and self.fp8_phase and self.fp8_phase_mx and isinstance(w, PackedWeight) and w.phase is not None and w.phase[0] == "out"
+        """MX-fp8 twin of a freshly prepared "out"-kind (``fp8_phase_mx``) or "in"-kind (``fp8_phase_in_mx``) phase copy, made HERE,
+        on the preparing stream, for the reason ``_with_mx8`` gives: never lazily at first use"""
+        if (self.fp8 and self.fp8_phase and isinstance(w, PackedWeight) and w.phase is not None
+                and ((self.fp8_phase_mx and w.phase[0] == "out") or (self.fp8_phase_in_mx and w.phase[0] == "in"))
                 and self.dtype == torch.bfloat16 and w.cin % 64 == 0 and w.cin >= self.fp8_min_cin):
             w.phase_mx8 = self.pack_mx8(w, phase=True)
         return w
@@ -471,7 +493,7 @@ class HipOps:
     def _conv_mx8(self, x, w, bias, y, *, ups, relu_in, mask, res, res_ups, res_scale, alpha, out_f32, pool_out, emit=None, alpha_dev=None,
                   relu_out=False, emit_bits=False, phase=False):
         n, hi, wi, cin = x.shape
-        if phase:                        # the "out" phase form: the twin of the 16-tap copy (always made with it: _with_phase_mx8)
+        if phase:                        # the "out" / "in" phase form: the twin of the 16-tap copy (always made with it: _with_phase_mx8)
             wmx = w.phase_mx8
         else:
             if w.mx8 is None:            # weights prepared before ops.fp8 was set (tests, benchmarks): single-stream use only
@@ -484,7 +506,8 @@ class HipOps:
         x8 = pre[0] if pre is not None and (pre[1] == "relu" or pre[1] == bool(relu_in)) else self.quantize_mx8(x, relu=relu_in)
         d = ConvDesc(n, hi, wi, cin, w.cout, 3, int(ups), 0, int(res_ups), int(out_f32), self.code, float(alpha),
                      float(res_scale), 1 | (16 if phase else 0), int(pool_out), int(relu_out), 0, 0, 0, alpha_dev.data_ptr() if alpha_dev is not None else None)
-        ws_bytes = self.lib.xmc_conv2d_mx8_workspace_bytes(C.byref(d)) if not getattr(self, "no_split_k", False) else 0
+        ws_query = self.lib.xmc_conv2d_mx8_phase_in_workspace_bytes if phase == "in" else self.lib.xmc_conv2d_mx8_workspace_bytes
+        ws_bytes = ws_query(C.byref(d)) if not getattr(self, "no_split_k", False) else 0
         ws = self.empty((ws_bytes // 4,), torch.float32) if ws_bytes else None
         y8 = None
         if (emit is not None and not ws_bytes and not out_f32 and w.cout % 64 == 0 and w.cout >= self.fp8_min_cin and self._mx8_patch_fits(y.shape[1], y.shape[2])
@@ -497,11 +520,18 @@ class HipOps:
                 mbits = mb
             if emit_bits and not out_f32:
                 ybits = torch.empty(tuple(y.shape[:-1]) + (w.cout // 16,), dtype=torch.int16, device=self.device)
-        check(self.lib.xmc_conv2d_mx8_bits(C.byref(d), _p(x8), _p(wmx[0]), _p(wmx[1]), _p(bias), _p(mask), _p(res),
-                                           _p(y), _p(y8), int(bool(emit)), _p(ws), _p(mbits), _p(ybits), self._stream()),
-              "xmc_conv2d_mx8_bits")
-        self.last_conv_mx8_phase = bool(phase)
-        self.mx8_phase_launches += int(bool(phase))
+        if phase == "in":                # entry points of its own: on xmc_conv2d_mx8 this descriptor stays XMC_EINVAL
+            assert mask is None and mbits is None
+            check(self.lib.xmc_conv2d_mx8_phase_in_bits(C.byref(d), _p(x8), _p(wmx[0]), _p(wmx[1]), _p(bias), _p(res), _p(y), _p(y8),
+                                                        int(bool(emit)), _p(ws), _p(ybits), self._stream()), "xmc_conv2d_mx8_phase_in_bits")
+            self.last_conv_mx8_phase_in = True
+            self.mx8_phase_in_launches += 1
+        else:
+            check(self.lib.xmc_conv2d_mx8_bits(C.byref(d), _p(x8), _p(wmx[0]), _p(wmx[1]), _p(bias), _p(mask), _p(res),
+                                               _p(y), _p(y8), int(bool(emit)), _p(ws), _p(mbits), _p(ybits), self._stream()),
+                  "xmc_conv2d_mx8_bits")
+            self.last_conv_mx8_phase = bool(phase)
+            self.mx8_phase_launches += int(bool(phase))
         if y8 is not None:
             y.mx8 = (y8, "relu" if relu_out else bool(emit))
         if ybits is not None:

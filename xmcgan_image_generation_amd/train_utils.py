@@ -92,6 +92,8 @@ def create_train_state(config, rng, init_batch=None, ops=None):
         ops.set_fp8_scale_rule(config.get("fp8_scale_rule", "next_binade"))
         if config.get("conv_fp8_phase", False):      # ... and the "out"-form phase launches on conv_phase_mx8_kernel (XMC_FP8_PHASE_MX=1 too)
             ops.fp8_phase_mx = True
+        if config.get("conv_fp8_phase_in", False):   # ... and the "in"-form ones on conv_phase_in_mx8_kernel (XMC_FP8_PHASE_IN_MX=1 too)
+            ops.fp8_phase_in_mx = True
     generator = _NetFactory(xmc_net.Generator, config, dtype, ops)
     discriminator = _NetFactory(xmc_net.Discriminator, config, dtype, ops)
     seed = int(rng)
