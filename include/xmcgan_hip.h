@@ -38,7 +38,7 @@ extern "C" {
 #define XMC_F32 0
 #define XMC_BF16 1
 
-#define XMC_ABI_VERSION 25
+#define XMC_ABI_VERSION 26
 int xmc_abi_version(void);
 
 /* Launch-heuristic knobs -- split-K workgroup targets and tile-selection thresholds whose defaults were A/B'd inside the
@@ -715,6 +715,42 @@ int xmc_maxpool3x3s2_valid(const void* x, void* y, int32_t n, int32_t hi, int32_
                            int32_t y_off, int32_t dtype, void* stream);
 int xmc_avgpool3x3_same(const void* x, void* y, int32_t n, int32_t h, int32_t w, int32_t c, int32_t dtype, void* stream);
 int xmc_mean_hw(const void* x, float* y, int32_t n, int32_t hw, int32_t c, int32_t dtype, void* stream);
+
+/* ------------------------------------------------------------------ BERT caption encoder (text in, embeddings out)
+ * The reference's preprocess_data.py:36-58 (get_bert_for_captions): bert_en_uncased_L-12_H-768_A-12 on [CLS] .. [SEP] rows of
+ * T = max_text_length ids, zero padded.  Everything here is float32; activations are [rows = n * t][h] and ALL t positions of
+ * every caption are computed (the reference's sentence embedding sums over the padded positions too, :57, and
+ * caption/embedding stores them).  The dense layers are xmc_gemm_f32 / xmc_gemm_f32_bf16mfma on the (out, in) weights; their
+ * biases are added by the kernels below that consume the products.  No result depends on which captions share a launch.
+ * Pointers are 16-byte aligned; XMC_EINVAL otherwise and for every size outside the stated domain (nothing is launched).
+ *
+ *  - xmc_bert_embed_ln: y[r] = LayerNorm(word[ids[r]] + pos[r mod t] + type[0]) * gamma + beta, the input of the first layer
+ *    (:55, segment ids all zero :53).  word (vocab, h), pos (npos, h) with t <= npos, type (>= 1, h).  The CALLER checks
+ *    0 <= ids[r] < vocab on the host before the launch; the kernel clamps an id into the table, so it never reads outside it.
+ *  - xmc_bias_residual_ln: y[r] = LayerNorm(x[r] + bias + res[r]) * gamma + beta (the two post-LN sites of a layer).
+ *    Both LayerNorms: biased variance as mean((v - mean)^2) over the row held in registers (two passes; with eps = 1e-12 the
+ *    one-pass E[v^2] - mean^2 gives variance 0 for a near-constant row), y = (v - mean) / sqrt(var + eps).  h % 4 == 0,
+ *    h <= 1024.  y may be x or res.
+ *  - xmc_bias_gelu: y = 0.5 v (1 + erf(v / sqrt 2)), v = x + bias[column] -- the exact-erf GELU of TF / HF, evaluated as
+ *    0.5 v erfc(-v / sqrt 2) in float64 and rounded once.  x, y (rows, f), f % 4 == 0; y may be x.
+ *  - xmc_bert_attention: qkv (n * t, 3 h) = the fused 3h-wide product [q | k | v] WITHOUT its bias, bias_qkv (3 h),
+ *    ctx (n * t, h).  Per caption and head (head dimension 64, heads = h / 64):
+ *    ctx = softmax_j((q + b_q)(k + b_k)^T / 8)(v + b_v), the softmax over the keys j < max_len[caption] only (in float32
+ *    identical to the reference's additive -10000 on the padded keys), for all t query rows, padded ones included.  The
+ *    scores stay in LDS.  Domain: 2 <= max_len[i] <= t <= 32, h % 64 == 0.  max_len (DEVICE, int32 [n]) is what the kernel
+ *    reads; max_len_host is the caller's HOST copy of the same n values, which this call validates before it launches
+ *    (XMC_EINVAL, nothing runs).  The kernel clamps what it reads to [1, t]: a stale device copy cannot index outside a tile.
+ *  - xmc_bert_sentence: out[i] = (sum over ALL t rows of emb[i], in row order) / max_len[i] (:56-57; max_len on the device),
+ *    emb (n * t, h), out (n, h), h % 4 == 0. */
+int xmc_bert_embed_ln(const int32_t* ids, const float* word, const float* pos, const float* type, const float* gamma,
+                      const float* beta, float* y, int32_t rows, int32_t t, int32_t h, int32_t vocab, int32_t npos, float eps,
+                      void* stream);
+int xmc_bias_residual_ln(const float* x, const float* bias, const float* res, const float* gamma, const float* beta, float* y,
+                         int32_t rows, int32_t h, float eps, void* stream);
+int xmc_bias_gelu(const float* x, const float* bias, float* y, int32_t rows, int32_t f, void* stream);
+int xmc_bert_attention(const float* qkv, const float* bias_qkv, const int32_t* max_len, const int32_t* max_len_host, float* ctx,
+                       int32_t n, int32_t t, int32_t h, void* stream);
+int xmc_bert_sentence(const float* emb, const int32_t* max_len, float* out, int32_t n, int32_t t, int32_t h, void* stream);
 
 #ifdef __cplusplus
 }

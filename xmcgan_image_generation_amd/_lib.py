@@ -18,7 +18,7 @@ LIB_PATH = os.path.join(_HERE, "libxmcgan_hip.so")
 PROBE_LIB_PATH = os.path.join(_HERE, "libxmc_probe.so")
 
 XMC_F32, XMC_BF16 = 0, 1
-ABI_VERSION = 25
+ABI_VERSION = 26
 
 
 class ConvDesc(C.Structure):
@@ -167,6 +167,11 @@ SIGNATURES = {
     "xmc_maxpool3x3s2_valid": [_P, _P, _I, _I, _I, _I, _I, _I, _I, _P],
     "xmc_avgpool3x3_same": [_P, _P, _I, _I, _I, _I, _I, _P],
     "xmc_mean_hw": [_P, _P, _I, _I, _I, _I, _P],
+    "xmc_bert_embed_ln": [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _F, _P],
+    "xmc_bias_residual_ln": [_P, _P, _P, _P, _P, _P, _I, _I, _F, _P],
+    "xmc_bias_gelu": [_P, _P, _P, _I, _I, _P],
+    "xmc_bert_attention": [_P, _P, _P, _P, _P, _I, _I, _I, _P],
+    "xmc_bert_sentence": [_P, _P, _P, _I, _I, _I, _P],
 }
 
 # diagnostic probes: include/xmc_probe.h, libxmc_probe.so (csrc_probe/) -- outside the product ABI

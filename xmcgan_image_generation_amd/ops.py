@@ -16,6 +16,7 @@ import ctypes as C
 import math
 import os
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -653,11 +654,12 @@ class HipOps:
             self._with_phase_mx8(wd)
 
     # -------------------------------------------------------------------------------------- GEMM
-    def gemm(self, a, b, *, ta=False, tb=False, alpha=1.0, alpha_dev=None, beta=0.0, out=None, fast=False):
+    def gemm(self, a, b, *, ta=False, tb=False, alpha=1.0, alpha_dev=None, beta=0.0, out=None, fast=False, split_k=True):
         """C = alpha * op(a) @ op(b) + beta * C over the last two dims (float32; 2-D or batched 3-D).
         ``a`` / ``b`` may be arbitrary strided views (no copies are made).  ``fast``: in the bf16 training mode
         the operands are rounded to bf16 inside the kernel and multiplied on the bf16 MFMA (float32 accumulate);
-        the float32 parity mode ignores the flag."""
+        the float32 parity mode ignores the flag.  ``split_k=False`` lends no split-K workspace: every output is one K range
+        whatever the row count (the caption encoder: a caption's rows must not depend on what else is in the chunk)."""
         assert a.dtype == b.dtype == torch.float32
         batched = a.dim() == 3
         if batched:
@@ -674,7 +676,7 @@ class HipOps:
         assert out.dtype == torch.float32 and out.stride(-1) == 1 and out.shape[-2:] == (am, bn)
         bf = fast and self.dtype == torch.bfloat16
         fn = self.lib.xmc_gemm_f32_bf16mfma if bf else self.lib.xmc_gemm_f32
-        wsn = self.lib.xmc_gemm_ws_floats(am, bn, ak, batch, int(bf))        # split-K scratch (few tiles, long K)
+        wsn = self.lib.xmc_gemm_ws_floats(am, bn, ak, batch, int(bf)) if split_k else 0      # split-K scratch (few tiles, long K)
         ws = self.empty((wsn,), torch.float32) if wsn else None
         check(fn(
             C.c_void_p(a.data_ptr()), C.c_void_p(b.data_ptr()), C.c_void_p(out.data_ptr()), am, bn, ak,
@@ -1497,6 +1499,58 @@ class HipOps:
         out = self.empty((n, c), torch.float32) if out is None else out
         assert out.dtype == torch.float32 and out.shape == (n, c)
         check(self.lib.xmc_mean_hw(_p(x), _p(out), n, h * w, c, _code(x.dtype), self._stream()), "xmc_mean_hw")
+        return out
+
+    # ------------------------------------------------------- BERT caption encoder (utils/bert_utils.py; float32 throughout)
+    def bert_embed_ln(self, ids, word, pos, type_, gamma, beta, out, t, eps=1e-12):
+        """out[r] = LN(word[ids[r]] + pos[r mod t] + type_[0]) * gamma + beta; ids int32 (rows,) ALREADY range-checked by the caller"""
+        rows, h = out.shape
+        assert ids.dtype == torch.int32 and ids.numel() == rows and out.dtype == word.dtype == torch.float32
+        assert word.shape[1] == pos.shape[1] == type_.shape[1] == h and out.is_contiguous()
+        check(self.lib.xmc_bert_embed_ln(_p(ids), _p(word), _p(pos), _p(type_), _p(gamma), _p(beta), _p(out), rows, t, h,
+                                         word.shape[0], pos.shape[0], float(eps), self._stream()), "xmc_bert_embed_ln")
+        return out
+
+    def bias_residual_ln(self, x, bias, res, gamma, beta, out=None, eps=1e-12):
+        """LN(x + bias + res) * gamma + beta over the last dim of (rows, h) float32"""
+        rows, h = x.shape
+        out = self.empty(x.shape, torch.float32) if out is None else out
+        assert x.dtype == res.dtype == out.dtype == torch.float32 and res.shape == x.shape == out.shape
+        assert x.is_contiguous() and res.is_contiguous() and out.is_contiguous() and bias.numel() == gamma.numel() == beta.numel() == h
+        check(self.lib.xmc_bias_residual_ln(_p(x), _p(bias), _p(res), _p(gamma), _p(beta), _p(out), rows, h, float(eps),
+                                            self._stream()), "xmc_bias_residual_ln")
+        return out
+
+    def bias_gelu(self, x, bias, out=None):
+        """exact-erf GELU of x + bias, (rows, f) float32; ``out`` may be ``x``"""
+        rows, f = x.shape
+        out = self.empty(x.shape, torch.float32) if out is None else out
+        assert x.dtype == out.dtype == torch.float32 and out.shape == x.shape and x.is_contiguous() and out.is_contiguous()
+        assert bias.numel() == f
+        check(self.lib.xmc_bias_gelu(_p(x), _p(bias), _p(out), rows, f, self._stream()), "xmc_bias_gelu")
+        return out
+
+    def bert_attention(self, qkv, bias_qkv, max_len, max_len_host, ctx, t):
+        """ctx (n * t, h) <- masked multi-head attention of the fused product qkv (n * t, 3 h) (bias added inside); ``max_len``: int32
+        (n,) on the device, ``max_len_host``: the same values as an int32 NumPy array (validated by the library before the launch)"""
+        rows, h3 = qkv.shape
+        n, h = rows // t, h3 // 3
+        mh = np.ascontiguousarray(max_len_host, dtype=np.int32)
+        assert rows == n * t and h3 == 3 * h and ctx.shape == (rows, h) and qkv.is_contiguous() and ctx.is_contiguous()
+        assert qkv.dtype == ctx.dtype == torch.float32 and max_len.dtype == torch.int32 and max_len.numel() == n == mh.size
+        assert bias_qkv.numel() == h3
+        check(self.lib.xmc_bert_attention(_p(qkv), _p(bias_qkv), _p(max_len), C.c_void_p(mh.ctypes.data), _p(ctx), n, t, h,
+                                          self._stream()), "xmc_bert_attention")
+        return ctx
+
+    def bert_sentence(self, emb, max_len, t, out=None):
+        """(n * t, h) -> (n, h): the sum over all t rows of a caption, in order, divided by max_len (int32, device)"""
+        rows, h = emb.shape
+        n = rows // t
+        out = self.empty((n, h), torch.float32) if out is None else out
+        assert rows == n * t and emb.dtype == out.dtype == torch.float32 and out.shape == (n, h) and emb.is_contiguous()
+        assert max_len.dtype == torch.int32 and max_len.numel() == n
+        check(self.lib.xmc_bert_sentence(_p(emb), _p(max_len), _p(out), n, t, h, self._stream()), "xmc_bert_sentence")
         return out
 
     def probe_layouts(self):

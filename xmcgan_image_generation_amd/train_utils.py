@@ -278,6 +278,18 @@ def eval_step(rng, state, batch, generator, config):
     return image, ema_image
 
 
+def generate_from_captions(rng, state, captions, generator, config, text_encoder):
+    """Text in, images out: ``captions`` (a list of strings) -> ``(image, ema_image)`` of ``eval_step``.  ``text_encoder``: a
+    ``utils.bert_utils.TextEncoder``.  The ``cond`` dict is built as ``coco_dataset.preprocess`` builds it (coco_dataset.py:127-167):
+    float32 ``embedding`` (N, T, 768) and ``sentence_embedding`` (N, 768), ``max_len`` as (N, 1) float."""
+    t = int(config.get("max_text_length", syn.MAX_WORDS))
+    embedding, sentence, max_len = text_encoder.get_bert_for_captions(list(captions), t)
+    batch = {"embedding": torch.as_tensor(embedding, dtype=torch.float32),
+             "sentence_embedding": torch.as_tensor(sentence, dtype=torch.float32),
+             "max_len": torch.as_tensor(max_len.astype("float32"))[:, None]}
+    return eval_step(rng, state, batch, generator, config)
+
+
 def generate_sample(rng, state, generator, config, cond=None, world_size=1):
     """Single-device sampling with a fresh ``z`` (reference train_utils.py:196-242) -> ``{"generated_image", "ema_generated_image"}``,
     each a ``make_grid`` of ``config.show_num`` images with the writer's leading [None] axis.  ``sample_size`` =
