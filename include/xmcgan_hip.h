@@ -38,7 +38,7 @@ extern "C" {
 #define XMC_F32 0
 #define XMC_BF16 1
 
-#define XMC_ABI_VERSION 26
+#define XMC_ABI_VERSION 27
 int xmc_abi_version(void);
 
 /* Launch-heuristic knobs -- split-K workgroup targets and tile-selection thresholds whose defaults were A/B'd inside the
@@ -751,6 +751,14 @@ int xmc_bias_gelu(const float* x, const float* bias, float* y, int32_t rows, int
 int xmc_bert_attention(const float* qkv, const float* bias_qkv, const int32_t* max_len, const int32_t* max_len_host, float* ctx,
                        int32_t n, int32_t t, int32_t h, void* stream);
 int xmc_bert_sentence(const float* emb, const int32_t* max_len, float* out, int32_t n, int32_t t, int32_t h, void* stream);
+
+/* ---- running sums of a training step's scalar metrics (the training loop; train_utils.MetricAccumulator) ----
+ * `vals` is a HOST array of n (1 <= n <= 8) device pointers to float32 scalars; they are passed to the kernel by value, so
+ * the array need not outlive the call.  One launch, one thread: sums[i] += (double)*vals[i] for i = 0 .. n-1 in index order
+ * (float64 adds), info[0] += 1, and if any value is NaN or +-inf and info[1] == 0, info[1] = info[0] (the 1-based call that
+ * first saw one).  sums: n doubles, info: 2 int32, both device memory the caller zeroes to start a window.  Captured into a
+ * hipGraph it accumulates once per replay. */
+int xmc_metrics_accum(const float* const* vals, int32_t n, double* sums, int32_t* info, void* stream);
 
 #ifdef __cplusplus
 }

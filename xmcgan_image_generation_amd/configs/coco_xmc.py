@@ -28,6 +28,14 @@ def get_config() -> ConfigDict:
     """Default 128 px configuration (reference coco_xmc.py:18-68)."""
     c = ConfigDict()
     c.seed = 42
+    # the training / evaluation loops (train_utils.train / test; coco_xmc.py:21-27,30-34,53-54)
+    c.num_train_steps = -1          # -1: num_epochs epochs of the training set
+    c.log_loss_every_steps = 1000
+    c.eval_every_steps = 1000       # train metrics + sample grids are written this often
+    c.checkpoint_every_steps = 5000
+    c.num_epochs = 500
+    c.dataset = "mscoco"
+    c.model_name = "xmc"
     c.beta1 = 0.5
     c.beta2 = 0.999
     c.d_lr = 0.0004
@@ -74,6 +82,11 @@ def get_test_config() -> ConfigDict:
     c.eval_batch_size = 2
     c.eval_num = 2                  # coco_xmc.py:76-77
     c.eval_avg_num = 1
+    c.num_train_steps = 2           # coco_xmc.py:78-81
+    c.log_loss_every_steps = 1
+    c.eval_every_steps = 1
+    c.checkpoint_every_steps = 1
+    c.num_epochs = 1
     c.show_num = 4                  # coco_xmc.py:85
     c.df_dim = 16
     c.gf_dim = 16

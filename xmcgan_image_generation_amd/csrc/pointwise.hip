@@ -470,4 +470,38 @@ extern "C" int xmc_adam_ema_dev_sn(float* p, float* g, float* m, float* v, float
     XMC_LAUNCH_RET();
 }
 
+// Running sums of a step's scalar metrics, kept on the device so that a replayed training graph needs no host read per step
+// (train_utils.MetricAccumulator).  The n <= 8 input pointers travel by value in the kernel arguments; ONE thread adds
+// *vals[i] to sums[i] in float64 in index order, counts the call in info[0] and records in info[1] the (1-based) first call
+// that saw a non-finite value.  Plain loads and stores: launches on one stream are ordered, nothing else touches the buffers.
+struct metric_ptrs { const float* p[8]; };
+
+__global__ void metrics_accum_kernel(metric_ptrs v, int n, double* sums, int* info) {
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    bool bad = false;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+        if (i < n) {
+            const float x = *v.p[i];
+            sums[i] += (double)x;
+            bad = bad || !(fabsf(x) <= 3.402823466e+38f);      // NaN and +-inf both fail the comparison
+        }
+    }
+    const int call = info[0] + 1;
+    info[0] = call;
+    if (bad && info[1] == 0) info[1] = call;
+}
+
+extern "C" int xmc_metrics_accum(const float* const* vals, int32_t n, double* sums, int32_t* info, void* stream) {
+    XMC_REQUIRE(vals && sums && info && n >= 1 && n <= 8);
+    XMC_REQUIRE(((uintptr_t)sums % 8) == 0 && ((uintptr_t)info % 4) == 0);
+    metric_ptrs v;
+    for (int i = 0; i < 8; ++i) {
+        v.p[i] = i < n ? vals[i] : nullptr;
+        XMC_REQUIRE(i >= n || (v.p[i] && ((uintptr_t)v.p[i] % 4) == 0));
+    }
+    hipLaunchKernelGGL(metrics_accum_kernel, dim3(1), dim3(1), 0, static_cast<hipStream_t>(stream), v, (int)n, sums, info);
+    XMC_LAUNCH_RET();
+}
+
 extern "C" int xmc_abi_version(void) { return XMC_ABI_VERSION; }

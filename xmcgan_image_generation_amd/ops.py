@@ -845,6 +845,16 @@ class HipOps:
         check(self.lib.xmc_add(_p(dst), _p(src), _p(dst), dst.numel(), _code(dst.dtype), self._stream()), "xmc_add")
         return dst
 
+    def metrics_accum(self, vals, sums, info):
+        """sums[i] += float64(vals[i]) for the (at most 8) float32 scalars ``vals``, info[0] += 1, info[1] = the first call that
+        saw a non-finite value: one single-thread launch on the current stream (capturable; the training loop's accumulator)"""
+        n = len(vals)
+        assert 1 <= n <= 8 and sums.dtype == torch.float64 and sums.numel() >= n and sums.is_contiguous()
+        assert info.dtype == torch.int32 and info.numel() >= 2 and info.is_contiguous()
+        assert all(v.dtype == torch.float32 and v.numel() == 1 and v.device == sums.device for v in vals)
+        ptrs = (C.c_void_p * n)(*[v.data_ptr() for v in vals])
+        check(self.lib.xmc_metrics_accum(ptrs, n, _p(sums), _p(info), self._stream()), "xmc_metrics_accum")
+
     def zeros_act(self, shape):
         """zero-filled tensor in the activation dtype (one memset)"""
         return torch.zeros(shape, dtype=self.dtype, device=self.device)

@@ -177,12 +177,13 @@ class GraphedTrainStep:
       the persistent flat buffers (``FlatTree``) at the end of the graph.
 
     Call the eager ``train_step`` at least once before constructing this (lazy per-device setup in the library,
-    RCCL communicator creation), then ``state, metrics = graphed(state, batch)``.  ``state`` must be the object
+    RCCL communicator creation), then ``state, metrics = graphed(state, batch)``.  ``accumulator`` (a ``MetricAccumulator``):
+    its launch is captured behind the step, so every replay also adds the step's metrics to the running sums.  ``state`` must be the object
     this instance returned last (or was built from): the graph owns the addresses of its tensors.
     """
 
     def __init__(self, state, batch, gan_model=xmc_gan, generator=None, discriminator=None, config=None,
-                 additional_data=None, grad_sync=None):
+                 additional_data=None, grad_sync=None, accumulator=None):
         g, d = generator(train=True), discriminator(train=True)
         ops = g.ops
         dev = ops.device
@@ -214,6 +215,8 @@ class GraphedTrainStep:
             new_state = xmc_gan._flush(new_state)
             bs.flat.copy_(new_state.generator_state["batch_stats"].flat)
             sn.flat.copy_(new_state.discriminator_state["spectral_norm_stats"].flat)
+            if accumulator is not None:                  # the step's metrics are summed on the device: still one graph launch
+                accumulator.add(metrics)
         # capture executed nothing: undo the host-side mirrors the Python code advanced, keep what a replay must add
         self._d_steps, self._g_steps = da.opt_step - before[1], ga.opt_step - before[0]
         self._steps = int(new_state.step) - before[2]
@@ -340,3 +343,274 @@ def generate_batch(rng, state, batch, generator, config, collect_all=False, grou
     return {"generated_image_batch": image_utils.make_grid(outs[0], show)[None],
             "ema_generated_image_batch": image_utils.make_grid(outs[1], show)[None],
             "ori_image_batch": image_utils.make_grid(outs[2], show)[None]}
+
+
+# ==================================================================================== the training and evaluation loops
+# (reference train_utils.py:312-514.  DESIGN.md section 9e lists every departure.)
+EVAL_KEYS = ("fid", "fid_std", "inception_score", "inception_score_std", "ema_fid", "ema_fid_std", "ema_inception_score",
+             "ema_inception_score_std")          # the order ``EvalMetric.calculate_inception_fid`` returns them in
+MAX_TO_KEEP = 5
+
+
+def fold_in(seed, *data):
+    """``jax.random.fold_in`` stand-in on integer seeds: a pure function of ``(seed, *data)``, 48 bits wide so that
+    ``train_step``'s ``rng * d_step_per_g_step + i`` stays a valid ``torch.Generator`` seed."""
+    import numpy as np
+    state = np.random.SeedSequence([int(seed) & 0xFFFFFFFFFFFFFFFF] + [int(d) for d in data])
+    return int(state.generate_state(1, np.uint64)[0] >> np.uint64(16))
+
+
+def rng_streams(seed):
+    """The independent streams both loops derive from ``config.seed`` (the reference splits one PRNGKey, :323-357,414): ``data``
+    (the rank is folded in by ``create_datasets``), ``model`` (``create_train_state``), ``train`` (folded with the step for the
+    eager ``train_step``), ``sample_batch`` (z of the sample grids, folded with the step), ``eval`` (``test``'s z)."""
+    return {name: fold_in(seed, i) for i, name in enumerate(("data", "model", "train", "sample_batch", "eval"))}
+
+
+def default_datasets(config, data_rng, start_step, rank, world, device):
+    """The ``datasets`` hook of ``train`` / ``test`` over the real pipeline.  A fresh run (``start_step`` 1) seeds the pipeline
+    with ``data_rng``; a run resumed at step ``s`` seeds it with ``fold_in(data_rng, s)`` -- the pipeline's position cannot be
+    checkpointed as the reference's tf.data iterator is, so a resumed run draws a new order instead of replaying the batches
+    the first run began with."""
+    from .libml import input_pipeline
+    seed = data_rng if start_step <= 1 else fold_in(data_rng, start_step)
+    return input_pipeline.create_datasets(config, seed, rank=rank, world=world, device=device)
+
+
+def resolve_num_train_steps(config, num_train_examples, local_devices=1, test_mode=False):
+    """``config.num_train_steps``, or for -1 the reference's rule (:339-352): ``mscoco`` trains ``num_epochs`` epochs of
+    ``num_train_examples // (local devices * d_step_per_g_step)`` steps; any other dataset trains its cardinality (here: the
+    hook's ``num_train_examples``), or one step in ``test_mode``."""
+    n = int(config.num_train_steps)
+    if n != -1:
+        return n
+    if config.get("dataset", "mscoco") == "mscoco":
+        steps_per_epoch = int(num_train_examples) // (int(local_devices) * int(config.d_step_per_g_step))
+        return steps_per_epoch * int(config.num_epochs)
+    return 1 if test_mode else int(num_train_examples)
+
+
+class MetricAccumulator:
+    """Float64 running sums of a step's scalar metrics, the number of steps added and the first step that held a non-finite
+    value, all in device memory: on ``HipOps`` one ``xmc_metrics_accum`` launch per ``add`` (capturable: ``GraphedTrainStep``
+    records it behind the step, so a replayed step needs no host read); on an operator table without ``metrics_accum`` the same
+    arithmetic in torch.  ``read`` is the only host synchronisation."""
+
+    def __init__(self, keys, ops=None, device=None):
+        self.keys = tuple(keys)
+        if not 1 <= len(self.keys) <= 8:
+            raise ValueError("MetricAccumulator holds 1 to 8 metrics")
+        self.ops = ops if hasattr(ops, "metrics_accum") else None
+        device = device if device is not None else (ops.device if ops is not None else torch.device("cpu"))
+        self.sums = torch.zeros((len(self.keys),), dtype=torch.float64, device=device)
+        self.info = torch.zeros((2,), dtype=torch.int32, device=device)         # [calls, 1-based first call with a non-finite value]
+
+    def add(self, metrics):
+        vals = [torch.as_tensor(metrics[k]).detach().reshape(-1) for k in self.keys]
+        if self.ops is not None:
+            self.ops.metrics_accum([v if v.dtype == torch.float32 else v.float() for v in vals], self.sums, self.info)
+            return
+        v = torch.cat([t.to(self.sums.device, torch.float32) for t in vals])
+        self.sums += v.double()
+        self.info[0] += 1
+        if not bool(torch.isfinite(v).all()) and int(self.info[1]) == 0:
+            self.info[1] = self.info[0]
+
+    def read(self):
+        """-> ({key: float64 sum}, number of ``add`` calls, first call with a non-finite value or 0)"""
+        sums = self.sums.cpu().tolist()
+        count, first_bad = self.info.cpu().tolist()
+        return dict(zip(self.keys, sums)), count, first_bad
+
+    def reset(self):
+        self.sums.zero_()
+        self.info.zero_()
+
+
+class CheckpointRotation:
+    """``ckpt-<n>.flax`` files of one directory: ``n`` is the save ordinal, continuing from the highest one present (the reference's
+    checkpoint library numbers its saves, not the steps); the newest ``max_to_keep`` are kept.  A file appears under its final
+    name only when it is complete (written under a temporary name, then renamed)."""
+
+    def __init__(self, directory, max_to_keep=MAX_TO_KEEP):
+        self.directory, self.max_to_keep = directory, int(max_to_keep)
+
+    def all(self):
+        from .utils import task_manager
+        return task_manager.list_checkpoints(self.directory)
+
+    def latest(self):
+        found = self.all()
+        return found[-1] if found else None
+
+    def save(self, state):
+        import os
+        from .utils import checkpoint, task_manager
+        os.makedirs(self.directory, exist_ok=True)
+        latest = self.latest()
+        n = task_manager.checkpoint_number(latest) + 1 if latest else 1
+        path = os.path.join(self.directory, f"ckpt-{n}.flax")
+        tmp = os.path.join(self.directory, f".ckpt-{n}.flax.tmp{os.getpid()}")
+        checkpoint.save(tmp, state)
+        os.replace(tmp, path)
+        for old in self.all()[:-self.max_to_keep]:
+            os.remove(old)
+        return path
+
+
+class JsonlWriter:
+    """Scalars as one JSON object per line (``{"step": s, name: value, ...}``), appended to ``path``."""
+
+    def __init__(self, path):
+        self.path = path
+
+    def write_scalars(self, step, scalars):
+        import json
+        with open(self.path, "a") as f:
+            f.write(json.dumps({"step": int(step), **{k: float(v) for k, v in scalars.items()}}) + "\n")
+
+
+def write_image_grids(directory, step, image_dict):
+    """Each ``(1, H, W, 3)`` float grid of ``generate_batch`` (values in [0, 1]) as ``<directory>/<name>_<step>.png``"""
+    import os
+    from .libml import png
+    os.makedirs(directory, exist_ok=True)
+    paths = {}
+    for name, grid in image_dict.items():
+        px = (grid[0].detach().float().clamp(0, 1) * 255.0).round().to(torch.uint8).cpu().numpy()
+        paths[name] = os.path.join(directory, f"{name}_{int(step):08d}.png")
+        tmp = paths[name] + ".tmp"
+        with open(tmp, "wb") as f:
+            f.write(png.encode_rgb(px))
+        os.replace(tmp, paths[name])
+    return paths
+
+
+def _rank_world():
+    import torch.distributed as dist
+    if dist.is_available() and dist.is_initialized():
+        return dist.get_rank(), dist.get_world_size(), True
+    return 0, 1, False
+
+
+def _array_fields(batch):
+    """the tensor fields of a pipeline batch (``return_text`` / ``return_filename`` add lists of bytes the step does not read)"""
+    import numpy as np
+    return {k: torch.as_tensor(v) for k, v in batch.items() if isinstance(v, (torch.Tensor, np.ndarray))}
+
+
+def train(config, workdir, test_mode=False, *, datasets=None):
+    """The training loop (reference train_utils.py:312-461).  Resumes from the newest checkpoint of ``workdir/checkpoints-0``;
+    every ``eval_every_steps`` (and on the last step) the averaged train metrics go to ``workdir/metrics.jsonl`` and three sample
+    grids to ``workdir/images/``; every ``checkpoint_every_steps`` (and on the last step) a checkpoint is written; ``TRAIN_DONE``
+    marks the end.  ``datasets``: ``(config, data_rng, start_step, rank, world, device) -> (train_iter, eval_iter,
+    num_train_examples)`` (default: ``default_datasets``).  On ``HipOps`` the first step of the call runs eagerly, the others
+    replay one captured graph with the metric accumulator inside; on an injected operator table every step runs eagerly.
+    With ``torch.distributed`` initialised the gradients are exchanged through ``dp.GradSync`` and rank 0 alone writes files.
+    Returns the final ``TrainState``."""
+    import os
+    from .utils import checkpoint, task_manager
+    rank, world, distributed = _rank_world()
+    writes = rank == 0
+    if config.get("model_name", "xmc") != "xmc":
+        raise NotImplementedError(f"{config.model_name} was not Implemented!")
+    gan_model = xmc_gan
+    if writes:
+        os.makedirs(workdir, exist_ok=True)
+    streams = rng_streams(config.seed)
+    additional_data = gan_model.create_additional_data(config)
+    generator, discriminator, state = create_train_state(config, streams["model"])
+    ops = generator.ops
+    manager = task_manager.TaskManagerWithCsvResults(os.path.join(workdir, "checkpoints"))
+    rotation = CheckpointRotation(manager.model_dir)
+    latest = rotation.latest()
+    if latest is not None:
+        state = checkpoint.restore(latest, state)
+    initial_step = int(state.step) + 1
+    device = ops.device if ops.device.type == "cuda" else None
+    train_iter, _eval_iter, num_train_examples = (datasets or default_datasets)(config, streams["data"], initial_step, rank, world,
+                                                                                 device)
+    num_train_steps = resolve_num_train_steps(config, num_train_examples, int(os.environ.get("LOCAL_WORLD_SIZE", world)), test_mode)
+    grad_sync = None
+    if distributed:
+        from .dp import GradSync
+        grad_sync = GradSync()
+    if writes and initial_step == 1:                 # the reference's writer.write_hparams (:402-403)
+        import json
+        with open(os.path.join(workdir, "config.json"), "w") as f:
+            json.dump(dict(config), f, indent=1, sort_keys=True, default=str)
+    use_graph = ops.device.type == "cuda" and xmc_net._OPS_FACTORY is None
+    accumulator = MetricAccumulator(xmc_gan.METRIC_KEYS, ops)
+    writer = JsonlWriter(os.path.join(workdir, "metrics.jsonl"))
+    graphed, window_start = None, initial_step
+    n_split = config.d_step_per_g_step
+    for step in range(initial_step, num_train_steps + 1):
+        is_last_step = step == num_train_steps
+        batch = {k: v.to(ops.device) for k, v in _array_fields(next(train_iter)).items()}
+        if graphed is None:
+            state, metrics = train_step(fold_in(streams["train"], step), state, batch, gan_model, generator, discriminator, config,
+                                        additional_data, grad_sync=grad_sync)
+            accumulator.add(metrics)
+            if use_graph and not is_last_step:
+                graphed = GraphedTrainStep(state, batch, gan_model, generator, discriminator, config, additional_data,
+                                           grad_sync=grad_sync, accumulator=accumulator)
+                state = graphed.state
+        else:
+            state, metrics = graphed(state, batch)
+        write_scalars = step % config.eval_every_steps == 0 or is_last_step
+        write_checkpoint = step % config.checkpoint_every_steps == 0 or is_last_step
+        if not (write_scalars or write_checkpoint):
+            continue
+        sums, count, first_bad = accumulator.read()
+        if first_bad:
+            raise FloatingPointError(f"train: a training metric was not finite at step {window_start + first_bad - 1}; "
+                                     f"no checkpoint of that state is written (the newest one is {rotation.latest()})")
+        state = xmc_gan._flush(state)
+        if write_scalars:
+            if writes:
+                writer.write_scalars(step, {k: sums[k] / count for k in accumulator.keys})
+            accumulator.reset()
+            window_start = step + 1
+            if writes:
+                visualize = split_input_dict(batch, n_split)[0]
+                grids = generate_batch(fold_in(streams["sample_batch"], step), state, visualize, generator, config)
+                write_image_grids(os.path.join(workdir, "images"), step, grids)
+        if write_checkpoint and writes:
+            rotation.save(state)
+    if writes:
+        manager.mark_training_done()
+    return state
+
+
+def test(config, workdir, *, datasets=None, inception_ckpt_path=None, inception=None, timeout=24 * 3600, task_manager_kw=None):
+    """The evaluation loop (reference train_utils.py:464-514): FID and Inception Score, from the current and from the EMA
+    parameters, of every checkpoint of ``workdir/checkpoints-0`` that has no row in its ``scores.csv`` yet; waits for new
+    checkpoints until ``timeout`` seconds pass without one or ``TRAIN_DONE`` appears.  The eight values go as ``eval/<name>`` to
+    ``scores.csv`` and to ``workdir/metrics.jsonl``.  ``inception`` / ``inception_ckpt_path``: see ``EvalMetric`` (which is built
+    when the first checkpoint is found).  Returns the number of checkpoints evaluated."""
+    import os
+    import torch.distributed as dist
+    from .utils import checkpoint, eval_metrics, task_manager
+    rank, world, distributed = _rank_world()
+    streams = rng_streams(config.seed)
+    generator, _, state = create_train_state(config, streams["model"])
+    ops = generator.ops
+    device = ops.device if ops.device.type == "cuda" else None
+    _, eval_iter, _ = (datasets or default_datasets)(config, streams["data"], 1, rank, world, device)
+    manager = task_manager.TaskManagerWithCsvResults(os.path.join(workdir, "checkpoints"), **(task_manager_kw or {}))
+    writer = JsonlWriter(os.path.join(workdir, "metrics.jsonl"))
+    eval_metric, done = None, 0
+    for path in manager.unevaluated_checkpoints(timeout=timeout):
+        if eval_metric is None:
+            eval_metric = eval_metrics.EvalMetric(eval_iter, config, inception_ckpt_path=inception_ckpt_path, inception=inception,
+                                                  chunk=int(config.get("eval_chunk", 256)),
+                                                  group=dist.group.WORLD if distributed else None)
+        state = checkpoint.restore(path, state)
+        values = eval_metric.calculate_inception_fid(generator, state, streams["eval"])
+        result = {f"eval/{k}": v for k, v in zip(EVAL_KEYS, values)}
+        if rank == 0:
+            os.makedirs(workdir, exist_ok=True)
+            manager.add_eval_result(path, result, -1)
+            writer.write_scalars(int(state.step), result)
+        done += 1
+    return done
