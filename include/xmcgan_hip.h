@@ -38,7 +38,7 @@ extern "C" {
 #define XMC_F32 0
 #define XMC_BF16 1
 
-#define XMC_ABI_VERSION 27
+#define XMC_ABI_VERSION 28
 int xmc_abi_version(void);
 
 /* Launch-heuristic knobs -- split-K workgroup targets and tile-selection thresholds whose defaults were A/B'd inside the
@@ -337,6 +337,21 @@ int xmc_bn_batch_stats(const void* x, float* ws, float* mean, float* rstd, float
                        int32_t update_running, void* stream);
 int xmc_bn_from_running(const float* run_mean, const float* run_var, float* mean, float* rstd,
                         int32_t c, float eps, void* stream);
+/* Cross-replica BatchNorm groups (ABI 28; flax nn.BatchNorm(axis_name="batch", axis_index_groups=groups),
+ * xmcgan/nets/xmc_net.py:192-201): the statistics pass split at the point where the replicas of a group exchange.
+ * xmc_bn_batch_sums: the two stages of xmc_bn_batch_stats stopped at sums[2c] = {sum x, sum x^2} of this replica
+ *   (ws: xmc_bn_stats_ws_floats(pixels, c) floats; same partial geometry, same fixed order, no atomics, nothing to zero).
+ * xmc_bn_finalize_rows: rows[g][2c], one such row per replica in rank order, added in a fixed order (row r in lane group
+ *   r % 16, the groups in index order: plain index order for g <= 16) and finalized with 1 / (g * pixels_per_row) by the
+ *   kernel that finalizes xmc_bn_batch_stats: the same bits on every replica; g == 1 is bit-equal to xmc_bn_batch_stats.
+ * xmc_rows_mean: out[i] = (sum_r rows[r][i]) / g in the same order -- the group mean of the backward sums s[2c] of
+ *   xmc_cbn_bwd_sums (xmc_cbn_act_bwd_dx divides by the local pixel count); g == 1: out is the row, bit for bit. */
+int xmc_bn_batch_sums(const void* x, float* ws, float* sums, int64_t pixels, int32_t c, int32_t dtype,
+                      void* stream);
+int xmc_bn_finalize_rows(const float* rows, int32_t g, float* mean, float* rstd, float* run_mean,
+                         float* run_var, int64_t pixels_per_row, int32_t c, float eps, float momentum,
+                         int32_t update_running, void* stream);
+int xmc_rows_mean(const float* rows, int32_t g, int32_t n, float* out, void* stream);
 /* gamma/beta: one row of c values per conditioning cell (n * hc * hc cells, hc | h; hc == 1:
  * per-sample conditional BN), rows `cstride` ELEMENTS apart (cstride >= c): gamma and beta are normally
  * the two halves of ONE (cells, 2c) conv / dense output (gamma = p, beta = p + c, cstride = 2c).

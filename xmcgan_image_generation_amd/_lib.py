@@ -18,7 +18,7 @@ LIB_PATH = os.path.join(_HERE, "libxmcgan_hip.so")
 PROBE_LIB_PATH = os.path.join(_HERE, "libxmc_probe.so")
 
 XMC_F32, XMC_BF16 = 0, 1
-ABI_VERSION = 27
+ABI_VERSION = 28
 
 
 class ConvDesc(C.Structure):
@@ -89,6 +89,9 @@ SIGNATURES = {
     "xmc_cbn_bwd_sums": [_P, _P, _P, _P, _P, _L, _I, _I, _I, _P],
     "xmc_bn_stats_ws_floats": [_L, _I],
     "xmc_bn_batch_stats": [_P, _P, _P, _P, _P, _P, _L, _I, _I, _F, _F, _I, _P],
+    "xmc_bn_batch_sums": [_P, _P, _P, _L, _I, _I, _P],
+    "xmc_bn_finalize_rows": [_P, _I, _P, _P, _P, _P, _L, _I, _F, _F, _I, _P],
+    "xmc_rows_mean": [_P, _I, _I, _P, _P],
     "xmc_cbn_act_bwd_dx": [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P],
     "xmc_pool2": [_P, _P, _P, _I, _I, _I, _I, _F, _I, _P],
     "xmc_pool2_relu": [_P, _P, _P, _P, _I, _I, _I, _I, _F, _I, _P],

@@ -835,6 +835,61 @@ extern "C" int xmc_bn_batch_stats(const void* x, float* ws, float* mean, float* 
     XMC_LAUNCH_RET();
 }
 
+// Cross-replica BatchNorm groups (flax nn.BatchNorm(axis_name="batch", axis_index_groups=...)): the two stages of
+// xmc_bn_batch_stats, stopped at the unscaled sums[2C] = {sum x, sum x^2} of THIS replica -- same partial geometry, same
+// fixed order, no atomics; sums needs no initialisation.  The replicas' rows are exchanged by the caller and finalized by
+// xmc_bn_finalize_rows.
+extern "C" int xmc_bn_batch_sums(const void* x, float* ws, float* sums, int64_t pixels, int32_t c, int32_t dtype,
+                                 void* stream) {
+    XMC_REQUIRE(x && ws && sums && pixels > 0 && c > 0 && c <= MAXC);
+    XMC_REQUIRE(dtype == XMC_F32 || dtype == XMC_BF16);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const bool vec = vec_ok(c, dtype, x);
+    long long rpb, blocks;
+    bn_partial_geometry(pixels, &rpb, &blocks);
+    dim3 grid((unsigned)blocks), block(256);
+    if (dtype == XMC_BF16) {
+        const bf16_t* xp = static_cast<const bf16_t*>(x);
+        if (vec) hipLaunchKernelGGL((bn_stats_kernel<bf16_t, 8>), grid, block, 0, s, xp, ws, (long long)pixels, c, (int)rpb, 1);
+        else hipLaunchKernelGGL((bn_stats_kernel<bf16_t, 1>), grid, block, 0, s, xp, ws, (long long)pixels, c, (int)rpb, 1);
+    } else {
+        const float* xp = static_cast<const float*>(x);
+        if (vec) hipLaunchKernelGGL((bn_stats_kernel<float, 4>), grid, block, 0, s, xp, ws, (long long)pixels, c, (int)rpb, 1);
+        else hipLaunchKernelGGL((bn_stats_kernel<float, 1>), grid, block, 0, s, xp, ws, (long long)pixels, c, (int)rpb, 1);
+    }
+    // (0 + 1 * total: the row total itself, bit for bit -- what reduce_rows_kernel<true> multiplies by 1 / pixels)
+    hipLaunchKernelGGL((reduce_rows_kernel<false>), dim3((2 * c + 15) / 16), dim3(256), 0, s, (const float*)ws, (int)blocks,
+                       2 * c, sums, (float*)nullptr, (float*)nullptr, (float*)nullptr, (float*)nullptr, 1.f, 0, 0.f, 0.f, 0);
+    XMC_LAUNCH_RET();
+}
+
+// rows[g][2C]: one xmc_bn_batch_sums row per replica of the group, in rank order.  The rows are added by the SAME kernel
+// that adds the partial rows of xmc_bn_batch_stats (row r in lane group r % 16, the 16 groups in index order: plain index
+// order for g <= 16) and finalized with 1 / (g * pixels_per_row): every replica computes the same bits from the same rows,
+// and g == 1 reproduces xmc_bn_batch_stats exactly.
+extern "C" int xmc_bn_finalize_rows(const float* rows, int32_t g, float* mean, float* rstd, float* run_mean,
+                                    float* run_var, int64_t pixels_per_row, int32_t c, float eps, float momentum,
+                                    int32_t update_running, void* stream) {
+    XMC_REQUIRE(rows && mean && rstd && g > 0 && pixels_per_row > 0 && c > 0 && c <= MAXC);
+    XMC_REQUIRE(!update_running || (run_mean && run_var));
+    const float p = (float)g * (float)pixels_per_row;           // (g == 1: (float)pixels, as in xmc_bn_batch_stats)
+    hipLaunchKernelGGL((reduce_rows_kernel<true>), dim3((c + 15) / 16), dim3(256), 0, static_cast<hipStream_t>(stream), rows,
+                       (int)g, 2 * c, (float*)nullptr, mean, rstd, run_mean, run_var, 1.0f / p, c, eps, momentum,
+                       update_running);
+    XMC_LAUNCH_RET();
+}
+
+// out[i] = (sum_r rows[r][i]) / g, rows in the fixed order of xmc_bn_finalize_rows: the group mean of the replicas'
+// backward sums s[2C] (the transpose of flax's pmean).  xmc_cbn_act_bwd_dx then divides by the LOCAL pixel count.
+// g == 1: out is the row, bit for bit.
+extern "C" int xmc_rows_mean(const float* rows, int32_t g, int32_t n, float* out, void* stream) {
+    XMC_REQUIRE(rows && out && g > 0 && n > 0);
+    hipLaunchKernelGGL((reduce_rows_kernel<false>), dim3((n + 15) / 16), dim3(256), 0, static_cast<hipStream_t>(stream), rows,
+                       (int)g, n, out, (float*)nullptr, (float*)nullptr, (float*)nullptr, (float*)nullptr,
+                       1.0f / (float)g, 0, 0.f, 0.f, 0);
+    XMC_LAUNCH_RET();
+}
+
 extern "C" int xmc_bn_finalize(const float* sums, float* mean, float* rstd, float* run_mean, float* run_var,
                                int64_t pixels, int32_t c, float eps, float momentum, int32_t update_running,
                                void* stream) {

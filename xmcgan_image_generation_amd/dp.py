@@ -15,6 +15,65 @@ import torch
 import torch.distributed as dist
 
 
+def check_schedule(schedule, bn_groups):
+    """Cross-replica BatchNorm groups (``BNGroups``) need the exclusive gradient schedule."""
+    if bn_groups is not None and schedule != "exclusive":
+        raise ValueError(
+            "batch_norm_group_size > 0 needs GradSync(schedule='exclusive'): under the overlapped schedule the gradient "
+            "exchange runs on a side stream beside the generator's passes, so the kernels of two communicators (gradient "
+            "group, BatchNorm group) sit in parallel branches and nothing makes every rank run them in the same order -- a "
+            "deadlock hazard")
+
+
+class BNGroups:
+    """The replica groups that share BatchNorm statistics (``config.batch_norm_group_size > 0``; flax
+    ``nn.BatchNorm(axis_name="batch", axis_index_groups=get_device_groups(...))``, reference xmc_net.py:192-201).
+
+    Every rank creates EVERY group with ``dist.new_group`` in the same order (the call is collective over the world) and keeps
+    its own: process groups of their own, never the gradient group, even where a group is the whole world.  Without
+    ``torch.distributed`` a group of one replica needs no exchange (the split kernels run with a single row); a larger one
+    cannot exist.  With it the collectives run even for a group of one: the only way a one-GPU machine exercises them.
+
+    ``gather_rows`` is an all-gather followed -- in the caller -- by a fixed-order sum (ops.bn_finalize_rows / ops.rows_mean),
+    not a sum all-reduce: a backend is free to add in any order, and here every rank of a group must compute the same bits
+    from the same rows, under gloo and RCCL alike."""
+
+    def __init__(self, config, world=None, rank=None):
+        from .utils.device_utils import config_groups
+        distributed = dist.is_available() and dist.is_initialized()
+        world, self.device_batch, self.groups = config_groups(config, world)
+        if rank is None:
+            rank = dist.get_rank() if distributed else 0
+        self.ranks = next(g for g in self.groups if rank in g)
+        self.size = len(self.ranks)
+        self.group = None
+        if distributed:
+            if world != dist.get_world_size():
+                raise ValueError(f"BNGroups: world ({world}) is not the initialised process group's size ({dist.get_world_size()})")
+            for g in self.groups:
+                pg = dist.new_group(g)
+                if rank in g:
+                    self.group = pg
+        elif self.size > 1:
+            raise ValueError(f"batch_norm_group_size ({config.batch_norm_group_size}) spans {self.size} replicas of batch "
+                             f"{self.device_batch}: that needs torch.distributed to be initialised")
+
+    def check_batch(self, b):
+        if int(b) != self.device_batch:
+            raise ValueError(f"the BatchNorm groups were built for a per-device batch of {self.device_batch} "
+                             f"(batch_norm_group_size {self.size * self.device_batch}), this generator call sees {int(b)}")
+
+    def gather_rows(self, row):
+        """row (n,) float32 -> (G, n): the rows of the group's replicas in rank order.  Issued on -- and synchronous with respect
+        to -- the current stream (the one the generator runs on); capturable like GradSync's exchanges."""
+        row = row.contiguous().view(-1)
+        if self.group is None:
+            return row.view(1, -1)
+        out = torch.empty((self.size, row.numel()), dtype=row.dtype, device=row.device)
+        dist.all_gather_into_tensor(out.view(-1), row, group=self.group)      # (the concatenated form: gloo takes no other)
+        return out
+
+
 class GradSync:
     """``transport="bf16"`` (optional, off by default: it changes the numerics the parity tests pin): the gradients travel
     as bfloat16 -- half the bytes on the xGMI links -- and are summed by RCCL in bfloat16; the
@@ -29,13 +88,15 @@ class GradSync:
                               with no contention term (a resident neighbour costs the convolution kernels 18-28 %, profiles/
                               r05_cu_contention.txt): the schedule that cannot lose to the overlap going wrong on real xGMI links."""
 
-    def __init__(self, bucket_elems=32 * 1024 * 1024, group=None, transport="float32", schedule="overlapped"):
+    def __init__(self, bucket_elems=32 * 1024 * 1024, group=None, transport="float32", schedule="overlapped", bn_groups=None):
         if not dist.is_initialized():
             raise RuntimeError("GradSync needs torch.distributed to be initialised")
         if transport not in ("float32", "bf16"):
             raise ValueError("transport is 'float32' or 'bf16'")
         if schedule not in ("overlapped", "exclusive"):
             raise ValueError("schedule is 'overlapped' or 'exclusive'")
+        self.bn_groups = bn_groups          # the BNGroups of the generator this exchange serves, or None
+        check_schedule(schedule, bn_groups)
         self.schedule = schedule
         self.group = group
         self.world = dist.get_world_size(group)
@@ -44,6 +105,12 @@ class GradSync:
         self._works = {}
         self._half = {}             # tag -> [(float32 slice, bf16 copy)] to widen back in wait()
         self._side = None
+
+    def require_groups(self, bn_groups):
+        """train_step's check: this exchange was built for the generator's BatchNorm groups and (still) runs the exclusive schedule"""
+        check_schedule(self.schedule, bn_groups)
+        if bn_groups is not self.bn_groups:
+            raise ValueError("the generator has BatchNorm groups: build GradSync(schedule='exclusive', bn_groups=generator(train=True).bn_groups)")
 
     @property
     def exclusive(self) -> bool:

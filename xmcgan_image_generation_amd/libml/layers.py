@@ -523,6 +523,14 @@ class BatchNormSite:
 
     def __init__(self, ops, path):
         self.ops, self.path = ops, path          # path of the BatchNorm_0 collection entry
+        self.groups = None                       # dp.BNGroups (config.batch_norm_group_size > 0), set by the generator
+
+    def reduce_s(self):
+        """The exchange of the backward pass (ops.cbn_act_bwd ``reduce_s``): the group mean of the replicas' channel sums --
+        the transpose of the forward pass's pmean -- or None without groups."""
+        if self.groups is None:
+            return None
+        return lambda s: self.ops.rows_mean(self.groups.gather_rows(s))
 
     def stats(self, x, batch_stats, new_batch_stats, train):
         ops = self.ops
@@ -535,6 +543,12 @@ class BatchNormSite:
             rm, rv = pre["mean"], pre["var"]
         else:
             rm, rv = st["mean"].clone(), st["var"].clone()
-        mean, rstd = ops.bn_batch_stats(x, rm, rv, True)
+        if self.groups is not None:
+            # cross-replica groups: [sum x, sum x^2] of this replica -> the group's rows in rank order -> fixed-order sum and
+            # finalize with 1 / (G * pixels): mean / var of the concatenated group batch, the same bits on every replica
+            rows = self.groups.gather_rows(ops.bn_batch_sums(x))
+            mean, rstd = ops.bn_finalize_rows(rows, x.numel() // x.shape[-1], rm, rv, True)
+        else:
+            mean, rstd = ops.bn_batch_stats(x, rm, rv, True)
         tree_set(new_batch_stats, self.path, {"mean": rm, "var": rv})
         return mean, rstd

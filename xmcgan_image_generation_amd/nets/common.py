@@ -63,10 +63,11 @@ class CondNorm:
         it untouched: their share is produced by ``FusedLocalGB.bwd`` once every site has written its slice)."""
         ops = self.ops
         x, mean, rstd, gb, hc, cond = tape
+        kw = {} if self.bn.groups is None else {"reduce_s": self.bn.reduce_s()}      # cross-replica BatchNorm groups
         if self.fused is not None:
-            dx, _ = ops.cbn_act_bwd(dy, x, mean, rstd, gb, hc, relu=True, dgb_out=self.fused.dgb_of(self))
+            dx, _ = ops.cbn_act_bwd(dy, x, mean, rstd, gb, hc, relu=True, dgb_out=self.fused.dgb_of(self), **kw)
             return dx, dcond
-        dx, dgb = ops.cbn_act_bwd(dy, x, mean, rstd, gb, hc, relu=True)
+        dx, dgb = ops.cbn_act_bwd(dy, x, mean, rstd, gb, hc, relu=True, **kw)
         if self.local:
             d = ops.cast(dgb.view(x.shape[0], hc, hc, -1), ops.dtype)
             self.gb.wgrad(cond, d)

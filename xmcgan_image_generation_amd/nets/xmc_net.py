@@ -78,8 +78,11 @@ def check_config(config):
         raise ValueError("d_spectral_norm=False (xmc_net.py:74-80) is not supported: the discriminator is built on "
                          "SpectralConv / SpectralDense as in every reference config")
     if config.get("batch_norm_group_size", -1) > 0:
-        raise ValueError("batch_norm_group_size > 0 (cross-replica BatchNorm groups, xmc_net.py:197-200 / "
-                         "utils/device_utils.py:18-26) is not supported: BatchNorm statistics are per replica")
+        # cross-replica BatchNorm groups (xmc_net.py:197-200 / utils/device_utils.py:18-26): the sizes must fit the per-device
+        # batch (config.batch_size // world, as create_datasets derives it) and the replicas that exist -- get_device_groups
+        # raises the ValueError otherwise (utils/device_utils.config_groups; e.g. a group batch that is no multiple of the per-device batch)
+        from ..utils.device_utils import config_groups
+        config_groups(config)
     if config.get("image_size") not in (128, 256):
         raise ValueError("image_size must be 128 or 256 (channel_dims are only defined for those, xmc_net.py:81-86,202-205)")
     if config.get("architecture", "xmc_net") != "xmc_net":
@@ -120,7 +123,22 @@ class _Net:
 
 # =================================================================================== generator
 class Generator(_Net):
-    """Generator network (reference xmc_net.py:145-248)."""
+    """Generator network (reference xmc_net.py:145-248).  ``bn_groups``: the ``dp.BNGroups`` of
+    ``config.batch_norm_group_size > 0``.  train_utils.create_train_state builds it once for every generator of its factory.
+    Constructed directly, the network builds its own only without ``torch.distributed`` (a group of one replica, no process
+    group); with it ``bn_groups`` is required: ``dist.new_group`` is collective, and networks that quietly created groups of
+    their own -- a train and an eval instance, or one on some ranks only -- would hang the others."""
+
+    def __init__(self, config, train, dtype=torch.float32, activation_fn=None, ops=None, bn_groups=None):
+        super().__init__(config, train, dtype=dtype, activation_fn=activation_fn, ops=ops)
+        if bn_groups is None and config.get("batch_norm_group_size", -1) > 0:
+            import torch.distributed as dist
+            if dist.is_available() and dist.is_initialized():
+                raise ValueError("batch_norm_group_size > 0 with torch.distributed initialised: pass bn_groups=dp.BNGroups(config), "
+                                 "built once on every rank (train_utils.create_train_state does)")
+            from ..dp import BNGroups
+            bn_groups = BNGroups(config)
+        self.bn_groups = bn_groups
 
     def shapes(self):
         return syn.generator_shapes(self.config)
@@ -145,6 +163,8 @@ class Generator(_Net):
         self.rgb = ConvSite(ops, arena, "Conv_1")
         self.local_gb = common.FusedLocalGB(ops, arena, [n for blk in self.sblocks for n in (blk.n0, blk.n1)] + [self.fnorm])
         self.global_gb = common.FusedGlobalGB(ops, arena, [n for blk in self.gblocks for n in (blk.n0, blk.n1)])
+        for site in self.bn_sites():
+            site.groups = self.bn_groups
         # one batched pass prepares every packable convolution weight (ops.wprep_*: fragment-ordered copies + the 16-tap phase
         # copies of the upsampling layers) whenever the parameters changed -- ~20 prep launches per step before
         self.wp, self._wp_ver = None, -1
@@ -210,6 +230,8 @@ class Generator(_Net):
         z = _to_dev(ops, z)
         b = z.shape[0]
         new_stats = FlatTree()
+        if train and self.bn_groups is not None:
+            self.bn_groups.check_batch(b)           # device_batch_size of get_device_groups is z.shape[0] (xmc_net.py:198)
         if train:
             prefill_running_stats(self.bn_sites(), batch_stats, new_stats)
         if self.wp is not None and self._wp_ver != arena.version:

@@ -723,6 +723,37 @@ class HipOps:
               "xmc_bn_batch_stats")
         return mean, rstd
 
+    # cross-replica BatchNorm groups (config.batch_norm_group_size > 0): bn_batch_stats split where the replicas exchange
+    def bn_batch_sums(self, x):
+        """-> sums (2C,) float32 = [sum x, sum x^2] of THIS replica: bn_batch_stats' two stages without the finalize."""
+        c = x.shape[-1]
+        pixels = x.numel() // c
+        ws = self.empty((self.lib.xmc_bn_stats_ws_floats(pixels, c),), torch.float32)
+        sums = self.empty((2 * c,), torch.float32)
+        check(self.lib.xmc_bn_batch_sums(_p(x), _p(ws), _p(sums), pixels, c, _code(x.dtype), self._stream()),
+              "xmc_bn_batch_sums")
+        return sums
+
+    def bn_finalize_rows(self, rows, pixels_per_row, run_mean, run_var, update, eps=1e-5, momentum=0.9):
+        """rows (G, 2C): one bn_batch_sums row per replica of the group, in rank order -> (mean, rstd) of the group batch;
+        updates the running statistics in place.  Fixed summation order: every replica computes the same bits."""
+        assert rows.dtype == torch.float32 and rows.dim() == 2 and rows.is_contiguous()
+        assert rows.shape[1] % 2 == 0, "rows are [sum | sum of squares]"
+        g, c = rows.shape[0], rows.shape[1] // 2
+        assert not update or (run_mean.numel() == c and run_var.numel() == c and run_mean.dtype == run_var.dtype == torch.float32)
+        mean, rstd = self.empty((c,), torch.float32), self.empty((c,), torch.float32)
+        check(self.lib.xmc_bn_finalize_rows(_p(rows), g, _p(mean), _p(rstd), _p(run_mean), _p(run_var), pixels_per_row, c,
+                                            eps, momentum, int(update), self._stream()), "xmc_bn_finalize_rows")
+        return mean, rstd
+
+    def rows_mean(self, rows):
+        """rows (G, n) float32 -> (n,): the mean over the rows, added in a fixed order."""
+        assert rows.dtype == torch.float32 and rows.dim() == 2 and rows.is_contiguous()
+        g, n = rows.shape
+        out = self.empty((n,), torch.float32)
+        check(self.lib.xmc_rows_mean(_p(rows), g, n, _p(out), self._stream()), "xmc_rows_mean")
+        return out
+
     def bn_from_running(self, run_mean, run_var, eps=1e-5):
         c = run_mean.numel()
         mean, rstd = self.empty((c,), torch.float32), self.empty((c,), torch.float32)
@@ -758,8 +789,10 @@ class HipOps:
                                        w, c, hc, cs, int(relu), _code(x.dtype), _code(g2.dtype), self._stream()), "xmc_cbn_act_fwd")
         return y
 
-    def cbn_act_bwd(self, dy, x, mean, rstd, gb, hc, relu=True, dgb_out=None):
-        """-> (dx, dgb) with dgb laid out like gb -- same dtype -- (written into ``dgb_out`` -- same rows / stride rules -- if given)."""
+    def cbn_act_bwd(self, dy, x, mean, rstd, gb, hc, relu=True, dgb_out=None, reduce_s=None):
+        """-> (dx, dgb) with dgb laid out like gb -- same dtype -- (written into ``dgb_out`` -- same rows / stride rules -- if given).
+        ``reduce_s`` (cross-replica BatchNorm groups): s (2C,) -> s, applied to the channel sums between the sums pass and the
+        dx pass -- the group mean over the replicas' sums; ``mean`` / ``rstd`` are then the group's statistics."""
         n, h, w, c = x.shape
         assert dy.dtype == x.dtype and dy.shape == x.shape
         g2, cs = self._gb_rows(gb, n, hc, c)
@@ -777,6 +810,9 @@ class HipOps:
         s = self.empty((2 * c,), torch.float32)
         ws = self.empty((self.lib.xmc_cbn_bwd_sums_ws_floats(n * hc * hc, c),), torch.float32)
         check(self.lib.xmc_cbn_bwd_sums(g_, dg_, db_, _p(s), _p(ws), n * hc * hc, c, cs, gcode, st), "xmc_cbn_bwd_sums")
+        if reduce_s is not None:
+            s = reduce_s(s)
+            assert s.dtype == torch.float32 and s.numel() == 2 * c and s.is_contiguous()
         dx = torch.empty_like(x)
         check(self.lib.xmc_cbn_act_bwd_dx(_p(dy), _p(x), _p(mean), _p(rstd), g_, b_, _p(s), _p(dx), n, h, w, c, hc,
                                           cs, int(relu), code, gcode, st), "xmc_cbn_act_bwd_dx")

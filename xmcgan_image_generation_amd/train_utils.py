@@ -56,13 +56,13 @@ class _NetFactory:
     """``functools.partial(generator_cls, config=..., dtype=...)`` of the reference
     (train_utils.py:159-161): called with ``train=`` it returns the (cached) network object."""
 
-    def __init__(self, cls, config, dtype, ops):
-        self.cls, self.config, self.dtype, self.ops = cls, config, dtype, ops
+    def __init__(self, cls, config, dtype, ops, **kw):
+        self.cls, self.config, self.dtype, self.ops, self.kw = cls, config, dtype, ops, kw
         self._cache = {}
 
     def __call__(self, train):
         if train not in self._cache:
-            self._cache[train] = self.cls(self.config, train, dtype=self.dtype, ops=self.ops)
+            self._cache[train] = self.cls(self.config, train, dtype=self.dtype, ops=self.ops, **self.kw)
         return self._cache[train]
 
 
@@ -94,7 +94,11 @@ def create_train_state(config, rng, init_batch=None, ops=None):
             ops.fp8_phase_mx = True
         if config.get("conv_fp8_phase_in", False):   # ... and the "in"-form ones on conv_phase_in_mx8_kernel (XMC_FP8_PHASE_IN_MX=1 too)
             ops.fp8_phase_in_mx = True
-    generator = _NetFactory(xmc_net.Generator, config, dtype, ops)
+    g_kw = {}
+    if config.get("batch_norm_group_size", -1) > 0:  # cross-replica BatchNorm groups: built ONCE (dist.new_group is collective)
+        from .dp import BNGroups
+        g_kw["bn_groups"] = BNGroups(config)
+    generator = _NetFactory(xmc_net.Generator, config, dtype, ops, **g_kw)
     discriminator = _NetFactory(xmc_net.Discriminator, config, dtype, ops)
     seed = int(rng)
     g_vars = generator(train=False).init(seed, None)
@@ -132,6 +136,8 @@ def train_step(rng, state, batch, gan_model=xmc_gan, generator=None, discriminat
     """One G+D training step (train_utils.py:91-130): the per-device batch (leading dim
     B * d_step_per_g_step) is split; ``train_d`` runs on the first halves, ``train_g_d`` on the last."""
     n = config.d_step_per_g_step
+    if grad_sync is not None and config.get("batch_norm_group_size", -1) > 0:
+        grad_sync.require_groups(generator(train=True).bn_groups)
     parts = split_input_dict(batch, n)
     rngs = [int(rng) * n + i for i in range(n)]      # one stream per half step (train_utils.py:121 splits the key)
     if (gan_model is xmc_gan and xmc_gan._RESNET_REAL_EARLY and grad_sync is None and n > 1 and additional_data
@@ -534,7 +540,10 @@ def train(config, workdir, test_mode=False, *, datasets=None):
     grad_sync = None
     if distributed:
         from .dp import GradSync
-        grad_sync = GradSync()
+        bn_groups = generator(train=True).bn_groups
+        # cross-replica BatchNorm groups issue collectives from inside the generator's passes: only the exclusive schedule
+        # keeps the gradient exchange out of their way (dp.check_schedule)
+        grad_sync = GradSync(schedule="exclusive", bn_groups=bn_groups) if bn_groups is not None else GradSync()
     if writes and initial_step == 1:                 # the reference's writer.write_hparams (:402-403)
         import json
         with open(os.path.join(workdir, "config.json"), "w") as f:
