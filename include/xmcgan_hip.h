@@ -38,7 +38,7 @@ extern "C" {
 #define XMC_F32 0
 #define XMC_BF16 1
 
-#define XMC_ABI_VERSION 28
+#define XMC_ABI_VERSION 29
 int xmc_abi_version(void);
 
 /* Launch-heuristic knobs -- split-K workgroup targets and tile-selection thresholds whose defaults were A/B'd inside the
@@ -423,8 +423,10 @@ int xmc_attn_g_fwd(const void* region, const float* words_n, const float* max_le
 int xmc_attn_g_bwd(const void* dctx, const void* region, const float* words_n, const float* attn,
                    const float* rinv, void* dregion, int32_t b, int32_t r, int32_t t, int32_t e,
                    float gamma, int32_t dtype, void* stream);
-/* attention_for_g on the matrix cores (bf16 tensors; r % 128 == 0, e % 64 == 0, t <= 32 -- xmc_attn_g_mfma_supported): both
- * products as MFMA 32x32x16 tiles with the words as the A operand, softmax in registers, float32 accumulation; same
+/* attention_for_g on the matrix cores (bf16 tensors; r % 128 == 0, e % 64 == 0, t <= 64 -- xmc_attn_g_mfma_supported): both
+ * products as MFMA 32x32x16 tiles with the words as the A operand, softmax in registers, float32 accumulation.  t <= 32 runs
+ * the one-word-block kernels; 32 < t <= 64 (Localized Narratives) the two-block kernels, which stage the words and then the
+ * transposed words in ONE LDS region in turn (144 e bytes, e <= 1088).  Same
  * arguments and results as xmc_attn_g_fwd / xmc_attn_g_bwd with dtype = XMC_BF16 (the float32 parity mode keeps those: the
  * attention indices are held bit-exact against the float32 oracle there). */
 int xmc_attn_g_mfma_supported(int32_t b, int32_t r, int32_t t, int32_t e);
@@ -755,6 +757,8 @@ int xmc_mean_hw(const void* x, float* y, int32_t n, int32_t hw, int32_t c, int32
  *    scores stay in LDS.  Domain: 2 <= max_len[i] <= t <= 32, h % 64 == 0.  max_len (DEVICE, int32 [n]) is what the kernel
  *    reads; max_len_host is the caller's HOST copy of the same n values, which this call validates before it launches
  *    (XMC_EINVAL, nothing runs).  The kernel clamps what it reads to [1, t]: a stale device copy cannot index outside a tile.
+ *  - xmc_bert_attention_long: the same arguments, semantics and checks for 2 <= max_len[i] <= t <= 64 (64-token captions):
+ *    one 256-thread workgroup per (caption, head), the probabilities [t][65] in LDS, float32 throughout.
  *  - xmc_bert_sentence: out[i] = (sum over ALL t rows of emb[i], in row order) / max_len[i] (:56-57; max_len on the device),
  *    emb (n * t, h), out (n, h), h % 4 == 0. */
 int xmc_bert_embed_ln(const int32_t* ids, const float* word, const float* pos, const float* type, const float* gamma,
@@ -765,6 +769,8 @@ int xmc_bias_residual_ln(const float* x, const float* bias, const float* res, co
 int xmc_bias_gelu(const float* x, const float* bias, float* y, int32_t rows, int32_t f, void* stream);
 int xmc_bert_attention(const float* qkv, const float* bias_qkv, const int32_t* max_len, const int32_t* max_len_host, float* ctx,
                        int32_t n, int32_t t, int32_t h, void* stream);
+int xmc_bert_attention_long(const float* qkv, const float* bias_qkv, const int32_t* max_len, const int32_t* max_len_host,
+                            float* ctx, int32_t n, int32_t t, int32_t h, void* stream);
 int xmc_bert_sentence(const float* emb, const int32_t* max_len, float* out, int32_t n, int32_t t, int32_t h, void* stream);
 
 /* ---- running sums of a training step's scalar metrics (the training loop; train_utils.MetricAccumulator) ----

@@ -18,7 +18,7 @@ LIB_PATH = os.path.join(_HERE, "libxmcgan_hip.so")
 PROBE_LIB_PATH = os.path.join(_HERE, "libxmc_probe.so")
 
 XMC_F32, XMC_BF16 = 0, 1
-ABI_VERSION = 28
+ABI_VERSION = 29
 
 
 class ConvDesc(C.Structure):
@@ -174,6 +174,7 @@ SIGNATURES = {
     "xmc_bias_residual_ln": [_P, _P, _P, _P, _P, _P, _I, _I, _F, _P],
     "xmc_bias_gelu": [_P, _P, _P, _I, _I, _P],
     "xmc_bert_attention": [_P, _P, _P, _P, _P, _I, _I, _I, _P],
+    "xmc_bert_attention_long": [_P, _P, _P, _P, _P, _I, _I, _I, _P],
     "xmc_bert_sentence": [_P, _P, _P, _I, _I, _I, _P],
     "xmc_metrics_accum": [_P, _I, _P, _P, _P],
 }

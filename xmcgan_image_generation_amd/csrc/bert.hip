@@ -7,6 +7,7 @@
 //   xmc_bias_residual_ln  y[r] = LN(x[r] + bias + res[r]) * gamma + beta             one wave per row
 //   xmc_bias_gelu         y = 0.5 v (1 + erf(v / sqrt 2)), v = x + bias              16 bytes per lane
 //   xmc_bert_attention    ctx = softmax_{j < max_len}((q + b_q)(k + b_k)^T / 8)(v + b_v)   one wave per (caption, head)
+//   xmc_bert_attention_long  the same for 2 <= T <= 64                                  one workgroup per (caption, head)
 //   xmc_bert_sentence     out[n] = sum_{t < T} emb[n][t] / max_len[n]                fixed order
 //
 // The row kernels hold the whole row in registers (16 bytes per lane per access, H <= 1024): the mean, then the variance as
@@ -22,6 +23,8 @@ constexpr int DH = 64;         // head dimension
 constexpr int KP = 68;         // LDS pitch of the q / k / v rows: 16-byte aligned, 16 rows cover the 64 banks once (ds_read_b128)
 constexpr int PP = 33;         // LDS pitch of the probabilities
 constexpr int ATT_MAX_T = 32;
+constexpr int PP_LONG = 65;    // LDS pitch of the probabilities, T <= 64
+constexpr int ATT_MAX_T_LONG = 64;
 
 struct RowLnArgs {
     const int32_t* ids; const float* word; const float* pos; const float* type;      // EMBED
@@ -186,6 +189,71 @@ __global__ __launch_bounds__(64) void bert_attention_kernel(const float* __restr
     }
 }
 
+// 2 <= T <= 64 (Localized Narratives, 64-token captions): one 256-thread workgroup per (caption, head).  The same LDS image as
+// above with the probabilities at pitch 65 (<= 67.3 KiB: two workgroups per CU); a wave owns one query row per pass and lane j
+// key j, so the softmax reductions span the wave; 16 lanes x 16 bytes finish one context row, 16 rows per pass.  float32
+// throughout, the keys added in ascending order, keys j >= max_len at probability exactly 0.
+__global__ __launch_bounds__(256) void bert_attention_long_kernel(const float* __restrict__ qkv, const float* __restrict__ bias,
+                                                                 const int32_t* __restrict__ max_len, float* __restrict__ ctx,
+                                                                 int T, int H) {
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    float* const Q = lds;
+    float* const K = Q + T * KP;
+    float* const V = K + T * KP;
+    float* const P = V + T * KP;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int heads = H / DH;
+    const int n = blockIdx.x / heads, hd = blockIdx.x - n * heads;
+    int ml = max_len[n];
+    ml = ml < 1 ? 1 : (ml > T ? T : ml);             // validated on the host copy; clamped so that no index can leave the tile
+    const int r = threadIdx.x >> 4, c4 = (threadIdx.x & 15) * 4;       // 16 rows per pass, 16 lanes x 16 bytes per row
+
+    {
+        const float4 bq = *reinterpret_cast<const float4*>(bias + hd * DH + c4);
+        const float4 bk = *reinterpret_cast<const float4*>(bias + H + hd * DH + c4);
+        const float4 bv = *reinterpret_cast<const float4*>(bias + 2 * H + hd * DH + c4);
+        for (int t = r; t < T; t += 16) {
+            const float* row = qkv + ((size_t)n * T + t) * (3 * (size_t)H) + hd * DH + c4;
+            *reinterpret_cast<float4*>(Q + t * KP + c4) = add4(*reinterpret_cast<const float4*>(row), bq);
+            *reinterpret_cast<float4*>(K + t * KP + c4) = add4(*reinterpret_cast<const float4*>(row + H), bk);
+            *reinterpret_cast<float4*>(V + t * KP + c4) = add4(*reinterpret_cast<const float4*>(row + 2 * H), bv);
+        }
+    }
+    __syncthreads();
+
+    {
+        const int j = lane;
+        const int jr = j < T ? j : T - 1;
+        const bool live = j < ml;
+        for (int i = wave; i < T; i += 4) {          // wave-uniform
+            float s = 0.f;
+#pragma unroll
+            for (int d = 0; d < DH; d += 4) {
+                const float4 qv = *reinterpret_cast<const float4*>(Q + i * KP + d);
+                const float4 kv = *reinterpret_cast<const float4*>(K + jr * KP + d);
+                s = fmaf(qv.x, kv.x, s); s = fmaf(qv.y, kv.y, s); s = fmaf(qv.z, kv.z, s); s = fmaf(qv.w, kv.w, s);
+            }
+            s = live ? s * 0.125f : -INFINITY;
+            const float m = wave_max(s);
+            const float e = live ? expf(s - m) : 0.f;
+            const float sum = wave_sum(e);
+            if (j < T) P[i * PP_LONG + j] = e / sum;
+        }
+    }
+    __syncthreads();
+
+    for (int i = r; i < T; i += 16) {                // ctx[i][d] = sum_{j < max_len} p[i][j] v[j][d], j ascending
+        float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+        for (int j = 0; j < ml; ++j) {
+            const float pj = P[i * PP_LONG + j];
+            const float4 vv = *reinterpret_cast<const float4*>(V + j * KP + c4);
+            acc.x = fmaf(pj, vv.x, acc.x); acc.y = fmaf(pj, vv.y, acc.y);
+            acc.z = fmaf(pj, vv.z, acc.z); acc.w = fmaf(pj, vv.w, acc.w);
+        }
+        *reinterpret_cast<float4*>(ctx + ((size_t)n * T + i) * H + hd * DH + c4) = acc;
+    }
+}
+
 // one thread per (caption, four channels): the T rows added in order, then divided by max_len (the reference divides the sum over
 // ALL T positions, padding included, by the number of real tokens)
 __global__ __launch_bounds__(256) void bert_sentence_kernel(const float* __restrict__ emb, const int32_t* __restrict__ max_len,
@@ -250,6 +318,22 @@ extern "C" int xmc_bert_attention(const float* qkv, const float* bias_qkv, const
     const size_t lds = (size_t)(3 * t * KP + t * PP) * sizeof(float);          // <= 30.3 KiB
     hipLaunchKernelGGL(bert_attention_kernel, dim3((unsigned)(n * (h / DH))), dim3(64), lds, static_cast<hipStream_t>(stream), qkv,
                        bias_qkv, max_len, ctx, t, h);
+    XMC_LAUNCH_RET();
+}
+
+extern "C" int xmc_bert_attention_long(const float* qkv, const float* bias_qkv, const int32_t* max_len, const int32_t* max_len_host,
+                                       float* ctx, int32_t n, int32_t t, int32_t h, void* stream) {
+    XMC_REQUIRE(qkv && bias_qkv && max_len && max_len_host && ctx);
+    XMC_REQUIRE(n > 0 && t >= 2 && t <= ATT_MAX_T_LONG && h >= DH && h % DH == 0);
+    XMC_REQUIRE((long long)n * (h / DH) < (1ll << 31));
+    XMC_REQUIRE(aligned16(qkv) && aligned16(bias_qkv) && aligned16(ctx));
+    for (int i = 0; i < n; ++i) XMC_REQUIRE(max_len_host[i] >= 2 && max_len_host[i] <= t);
+    const size_t lds = (size_t)(3 * t * KP + t * PP_LONG) * sizeof(float);     // <= 67.3 KiB: above the 64 KiB default
+    static XmcLdsOptIn opt_in;
+    if (!opt_in.ensure({reinterpret_cast<const void*>(&bert_attention_long_kernel)}, 3 * ATT_MAX_T_LONG * KP * 4 + ATT_MAX_T_LONG * PP_LONG * 4))
+        return XMC_EINVAL;
+    hipLaunchKernelGGL(bert_attention_long_kernel, dim3((unsigned)(n * (h / DH))), dim3(256), lds, static_cast<hipStream_t>(stream),
+                       qkv, bias_qkv, max_len, ctx, t, h);
     XMC_LAUNCH_RET();
 }
 

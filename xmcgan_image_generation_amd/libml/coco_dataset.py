@@ -29,6 +29,8 @@ class COCODataset:
         self.image_size, self.z_dim, self.data_dtype = image_size, z_dim, data_dtype
         self.data_dir, self.coco_version = data_dir, coco_version
         self.return_text, self.return_filename = return_text, return_filename
+        if coco_version == "ln":                     # Localized Narratives: one 64-token caption per image (coco_dataset.py:56-62)
+            sentence_num, max_text_length = 1, syn.LN_MAX_WORDS
         self.sentence_num = sentence_num
         self.embedding_shape = (sentence_num, max_text_length, embedding_dim)      # coco_dataset.py:62-63
 

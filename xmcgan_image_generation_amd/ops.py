@@ -1589,6 +1589,18 @@ class HipOps:
                                           self._stream()), "xmc_bert_attention")
         return ctx
 
+    def bert_attention_long(self, qkv, bias_qkv, max_len, max_len_host, ctx, t):
+        """``bert_attention`` for 2 <= t <= 64 (``xmc_bert_attention_long``: Localized Narratives' 64-token captions)"""
+        rows, h3 = qkv.shape
+        n, h = rows // t, h3 // 3
+        mh = np.ascontiguousarray(max_len_host, dtype=np.int32)
+        assert rows == n * t and h3 == 3 * h and ctx.shape == (rows, h) and qkv.is_contiguous() and ctx.is_contiguous()
+        assert qkv.dtype == ctx.dtype == torch.float32 and max_len.dtype == torch.int32 and max_len.numel() == n == mh.size
+        assert bias_qkv.numel() == h3
+        check(self.lib.xmc_bert_attention_long(_p(qkv), _p(bias_qkv), _p(max_len), C.c_void_p(mh.ctypes.data), _p(ctx), n, t, h,
+                                               self._stream()), "xmc_bert_attention_long")
+        return ctx
+
     def bert_sentence(self, emb, max_len, t, out=None):
         """(n * t, h) -> (n, h): the sum over all t rows of a caption, in order, divided by max_len (int32, device)"""
         rows, h = emb.shape

@@ -16,6 +16,7 @@ from __future__ import annotations
 import numpy as np
 
 MAX_WORDS = 17      # reference xmcgan/libml/dataset_constants.py:20
+LN_MAX_WORDS = 64   # coco_version = "ln" (Localized Narratives): one caption per image, 64 tokens (dataset_constants.py:19)
 EMB_DIM = 768       # BERT-base hidden size (preprocess_data.py)
 
 G_CHANNELS = {128: [16, 8, 4, 2, 1], 256: [16, 8, 8, 4, 2, 1]}
@@ -195,21 +196,23 @@ def init_discriminator(cfg, seed=43, bias_scale=0.0):
 
 
 # ------------------------------------------------------------------------------------- batches
-def make_batch(cfg, per_device_batch=None, rank=0, seed=1234, dtype=np.float32):
+def make_batch(cfg, per_device_batch=None, rank=0, seed=1234, dtype=np.float32, max_words=None):
     """One per-device batch for ``train_step``: leading dim = B * d_step_per_g_step.
 
     image U[0,1); embedding N(0,1) with all 17 rows non-zero (cosine_similarity in the
     reference has no epsilon, attention_lib.py:23-27); max_len integer in [4, 17] stored as
     float (coco_dataset.py:141,158); sentence_embedding = sum over all rows / max_len
-    (coco_dataset.py:142); z N(0,1) (coco_dataset.py:165-166).
+    (coco_dataset.py:142); z N(0,1) (coco_dataset.py:165-166).  ``max_words``: rows per caption (default 17;
+    ``LN_MAX_WORDS`` for Localized-Narratives-shaped batches), max_len then in [4, max_words].
     """
+    t = MAX_WORDS if max_words is None else int(max_words)
     b = per_device_batch if per_device_batch is not None else cfg["batch_size"]
     n = b * cfg["d_step_per_g_step"]
     hw = cfg["image_size"]
     rng = np.random.default_rng(seed + rank)
     image = rng.random((n, hw, hw, 3), dtype=np.float32)
-    emb = rng.standard_normal((n, MAX_WORDS, EMB_DIM)).astype(np.float32)
-    max_len = rng.integers(4, MAX_WORDS + 1, size=(n, 1)).astype(np.float32)
+    emb = rng.standard_normal((n, t, EMB_DIM)).astype(np.float32)
+    max_len = rng.integers(4, t + 1, size=(n, 1)).astype(np.float32)
     sent = (emb.sum(axis=1) / max_len).astype(np.float32)
     z = rng.standard_normal((n, cfg["z_dim"])).astype(np.float32)
     out = dict(image=image, image_aug=image.copy(), embedding=emb, max_len=max_len,

@@ -290,8 +290,11 @@ def eval_step(rng, state, batch, generator, config):
 def generate_from_captions(rng, state, captions, generator, config, text_encoder):
     """Text in, images out: ``captions`` (a list of strings) -> ``(image, ema_image)`` of ``eval_step``.  ``text_encoder``: a
     ``utils.bert_utils.TextEncoder``.  The ``cond`` dict is built as ``coco_dataset.preprocess`` builds it (coco_dataset.py:127-167):
-    float32 ``embedding`` (N, T, 768) and ``sentence_embedding`` (N, 768), ``max_len`` as (N, 1) float."""
-    t = int(config.get("max_text_length", syn.MAX_WORDS))
+    float32 ``embedding`` (N, T, 768) and ``sentence_embedding`` (N, 768), ``max_len`` as (N, 1) float.  T is
+    ``config.max_text_length`` if set, else 64 for ``coco_version == "ln"``, else 17."""
+    # the caption length the model was trained at: Localized Narratives (coco_version = "ln") pads to 64 tokens, COCO to 17
+    default_t = syn.LN_MAX_WORDS if config.get("coco_version", "2014") == "ln" else syn.MAX_WORDS
+    t = int(config.get("max_text_length", None) or default_t)
     embedding, sentence, max_len = text_encoder.get_bert_for_captions(list(captions), t)
     batch = {"embedding": torch.as_tensor(embedding, dtype=torch.float32),
              "sentence_embedding": torch.as_tensor(sentence, dtype=torch.float32),

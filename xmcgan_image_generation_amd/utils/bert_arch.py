@@ -14,6 +14,7 @@ import numpy as np
 HEAD_DIM = 64
 LN_EPS = 1e-12
 MAX_ATTENTION_T = 32          # xmc_bert_attention's domain
+MAX_ATTENTION_T_LONG = 64     # xmc_bert_attention_long's (Localized Narratives captions)
 
 EMBEDDING_KEYS = ("embeddings.word_embeddings.weight", "embeddings.position_embeddings.weight",
                   "embeddings.token_type_embeddings.weight", "embeddings.LayerNorm.weight", "embeddings.LayerNorm.bias")

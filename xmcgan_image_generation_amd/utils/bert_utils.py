@@ -72,14 +72,15 @@ def bert_model(checkpoint_path, seed: int = 0, **init_kw):
     return {k: np.ascontiguousarray(raw[k], dtype=np.float32) for k in keep}
 
 
-def check_ids(ids, max_len, vocab, max_pos):
-    """host-side domain check of a batch of id rows; raises ``ValueError`` before anything is launched"""
+def check_ids(ids, max_len, vocab, max_pos, max_t=arch.MAX_ATTENTION_T):
+    """host-side domain check of a batch of id rows; raises ``ValueError`` before anything is launched.  ``max_t``: the longest
+    row the caller's attention kernel serves (``MAX_ATTENTION_T_LONG`` where ``xmc_bert_attention_long`` is behind it)"""
     ids, max_len = np.asarray(ids), np.asarray(max_len)
     if ids.ndim != 2 or max_len.shape != (ids.shape[0],):
         raise ValueError(f"ids must be (N, T) and max_len (N,), got {ids.shape} and {max_len.shape}")
     t = ids.shape[1]
-    if not 2 <= t <= min(arch.MAX_ATTENTION_T, max_pos):
-        raise ValueError(f"max_text_length {t} outside 2..{min(arch.MAX_ATTENTION_T, max_pos)}")
+    if not 2 <= t <= min(max_t, max_pos):
+        raise ValueError(f"max_text_length {t} outside 2..{min(max_t, max_pos)}")
     if ids.size and (ids.min() < 0 or ids.max() >= vocab):
         bad = ids[(ids < 0) | (ids >= vocab)]
         raise ValueError(f"token id {int(bad[0])} outside the vocabulary 0..{vocab - 1}")
@@ -90,7 +91,7 @@ def check_ids(ids, max_len, vocab, max_pos):
 class BertEncoder:
     """``(ids (N, T) int, max_len (N,) int) -> embedding (N, T, hidden) float32`` (NumPy) on the HIP kernels.
 
-    Per layer: GEMM (q | k | v as one hidden -> 3 hidden product), ``xmc_bert_attention``, GEMM, ``xmc_bias_residual_ln``,
+    Per layer: GEMM (q | k | v as one hidden -> 3 hidden product), ``xmc_bert_attention`` (``_long`` for 32 < T <= 64), GEMM, ``xmc_bias_residual_ln``,
     GEMM, ``xmc_bias_gelu``, GEMM, ``xmc_bias_residual_ln``; ``xmc_bert_embed_ln`` in front.  The GEMMs get no split-K
     workspace and every other kernel works row by row or caption by caption, so a caption's embedding does not depend on
     what shares its chunk.  Captions are processed ``chunk`` at a time; the activation buffers are allocated once per chunk
@@ -144,7 +145,7 @@ class BertEncoder:
         this object, valid until the next call of the same shape"""
         ids = np.ascontiguousarray(ids, dtype=np.int64)
         ml = np.ascontiguousarray(max_len, dtype=np.int64)
-        check_ids(ids, ml, self.dims.vocab, self.dims.max_pos)
+        check_ids(ids, ml, self.dims.vocab, self.dims.max_pos, max_t=arch.MAX_ATTENTION_T_LONG)
         ops, (n, t) = self.ops, ids.shape
         b = self.buffers(n, t)
         ml32 = ml.astype(np.int32)
@@ -152,11 +153,12 @@ class BertEncoder:
         b["max_len"].copy_(torch.as_tensor(ml32))
         word, pos, typ, g, be = self.emb
         h, h1 = b["h"], b["h1"]
+        attention = ops.bert_attention if t <= arch.MAX_ATTENTION_T else ops.bert_attention_long     # 64-token narratives
         ops.bert_embed_ln(b["ids"], word, pos, typ, g, be, h, t, eps=arch.LN_EPS)
         self.launches += 1
         for L in self.layers:
             self._gemm(h, L["w_qkv"], b["qkv"])
-            ops.bert_attention(b["qkv"], L["b_qkv"], b["max_len"], ml32, b["ctx"], t)
+            attention(b["qkv"], L["b_qkv"], b["max_len"], ml32, b["ctx"], t)
             self._gemm(b["ctx"], L["w_ao"], b["proj"])
             ops.bias_residual_ln(b["proj"], L["b_ao"], h, L["w_ln1"], L["b_ln1"], out=h1, eps=arch.LN_EPS)
             self._gemm(h1, L["w_ff1"], b["ff"])
@@ -171,7 +173,8 @@ class BertEncoder:
     def encode(self, ids, max_len):
         """-> (embedding (N, T, hidden), sentence_embedding (N, hidden)) float32 NumPy, chunk by chunk"""
         ids, max_len = np.asarray(ids), np.asarray(max_len)
-        check_ids(ids, max_len, self.dims.vocab, self.dims.max_pos)          # the WHOLE list first: nothing runs on a bad one
+        check_ids(ids, max_len, self.dims.vocab, self.dims.max_pos,          # the WHOLE list first: nothing runs on a bad one
+                  max_t=arch.MAX_ATTENTION_T_LONG)
         n, t = ids.shape
         emb = np.empty((n, t, self.dims.hidden), np.float32)
         sent = np.empty((n, self.dims.hidden), np.float32)
