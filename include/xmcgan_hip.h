@@ -38,7 +38,7 @@ extern "C" {
 #define XMC_F32 0
 #define XMC_BF16 1
 
-#define XMC_ABI_VERSION 29
+#define XMC_ABI_VERSION 30
 int xmc_abi_version(void);
 
 /* Launch-heuristic knobs -- split-K workgroup targets and tile-selection thresholds whose defaults were A/B'd inside the
@@ -780,6 +780,47 @@ int xmc_bert_sentence(const float* emb, const int32_t* max_len, float* out, int3
  * first saw one).  sums: n doubles, info: 2 int32, both device memory the caller zeroes to start a window.  Captured into a
  * hipGraph it accumulates once per replay. */
 int xmc_metrics_accum(const float* const* vals, int32_t n, double* sums, int32_t* info, void* stream);
+
+/* ---- in-graph training statistics (config.train_statistics; train_statistics.TrainStatistics; csrc/train_stats.hip, ABI 30) ----
+ * xmc_segment_sumsq: x is a flat float32 buffer of n elements, segs a DEVICE table of nseg (offset, length) int64 pairs in
+ *   elements; per segment s it writes sumsq[s] = sum of x[i]^2 over the segment (products and adds in float64) and
+ *   nonfinite[s] = its number of NaN / +-inf elements (int32, saturating).  Offsets and lengths need no alignment, a length may
+ *   be 0, segments may overlap.  Two kernels through the caller's workspace `ws` (xmc_segment_sumsq_ws_bytes of the table, 16-byte
+ *   aligned): pieces of 8192 elements summed in a fixed order by one workgroup each, then one wave per segment adds its pieces
+ *   in a fixed order.  No atomics: two runs are bit-identical.  segs_host is the caller's HOST copy of the table, which this
+ *   call validates before it launches (every segment inside [0, n), the workspace large enough: XMC_EINVAL, nothing runs) and
+ *   sizes the grid from; the kernels read the device table and clamp what they read to the buffer.  x is 16-byte aligned.
+ * xmc_train_stats: ONE workgroup gathers the XMC_TRAIN_STATS_N float32 scalars of a training step into `vec` --
+ *   [3h + 0 / 1 / 2] = loss_vec[h], head_stats[h][0] (accuracy), head_stats[h][1] (entropy) of the five contrastive heads;
+ *   [15 .. 18] = mean of the b real logits (logits[0 .. b)), mean of the b generated ones, share of real logits < 1, share of
+ *   generated logits > -1; [19 .. 22] = d_grad_scale * sqrt(sum leaf_gsq[0 .. n_d)), g_grad_scale * sqrt(sum leaf_gsq[n_d ..
+ *   n_leaves)), sqrt(sum leaf_psq[0 .. n_d)), sqrt(sum leaf_psq[n_d .. n_leaves)); [23], [24] = min and max of scal[2 i] over
+ *   the n_sigma {sigma, 1 / (sigma + eps)} pairs (0 when there are none) -- and in the same launch adds vec to the float64
+ *   `sums`, adds leaf_gsq * grad_scale^2 / leaf_psq / leaf_bad to the window tables win_gsq / win_psq (float64) / win_bad
+ *   (int64), info[0] += 1, and if info[1] == 0 and a leaf_bad entry is non-zero: info[1] = info[0], info[2] = the first such
+ *   leaf.  The caller zeroes sums, info (4 int32) and the window tables to start a window.  Plain loads and stores. */
+#define XMC_TRAIN_STATS_N 25
+typedef struct {
+    const float* logits;      /* 2 b float32: D's logits, the real half first */
+    const float* scal;        /* 2 n_sigma float32 (may be NULL when n_sigma == 0) */
+    const float* loss_vec;    /* 5 float32 */
+    const float* head_stats;  /* 5 x 2 float32 */
+    const double* leaf_gsq;   /* n_leaves: per-tensor sum of squares of the gradient, D's n_d tensors first */
+    const double* leaf_psq;   /* n_leaves: ... of the parameters */
+    const int32_t* leaf_bad;  /* n_leaves: non-finite gradient elements */
+    float* vec;               /* XMC_TRAIN_STATS_N float32 */
+    double* sums;             /* XMC_TRAIN_STATS_N float64 */
+    int32_t* info;            /* 4 int32 */
+    double* win_gsq;          /* n_leaves */
+    double* win_psq;          /* n_leaves */
+    int64_t* win_bad;         /* n_leaves */
+    int32_t b, n_sigma, n_leaves, n_d;
+    float d_grad_scale, g_grad_scale;
+} xmc_train_stats_args;
+int64_t xmc_segment_sumsq_ws_bytes(const int64_t* segs_host, int32_t nseg);
+int xmc_segment_sumsq(const float* x, int64_t n, const int64_t* segs, const int64_t* segs_host, int32_t nseg, double* sumsq,
+                      int32_t* nonfinite, void* ws, int64_t ws_bytes, void* stream);
+int xmc_train_stats(const xmc_train_stats_args* a, void* stream);
 
 #ifdef __cplusplus
 }

@@ -18,7 +18,7 @@ LIB_PATH = os.path.join(_HERE, "libxmcgan_hip.so")
 PROBE_LIB_PATH = os.path.join(_HERE, "libxmc_probe.so")
 
 XMC_F32, XMC_BF16 = 0, 1
-ABI_VERSION = 29
+ABI_VERSION = 30
 
 
 class ConvDesc(C.Structure):
@@ -53,6 +53,16 @@ class WprepEntry(C.Structure):       # mirrors xmc_wprep_entry
                 ("part_off", C.c_int64), ("cout", C.c_int32), ("cin", C.c_int32), ("taps", C.c_int32), ("blk0", C.c_int32),
                 ("flags", C.c_int32), ("u_off", C.c_int32), ("v_off", C.c_int32), ("blk_c", C.c_int32)]
 
+
+class TrainStatsArgs(C.Structure):   # mirrors xmc_train_stats_args
+    _fields_ = [(n, C.c_void_p) for n in
+                ("logits", "scal", "loss_vec", "head_stats", "leaf_gsq", "leaf_psq", "leaf_bad", "vec", "sums", "info", "win_gsq",
+                 "win_psq", "win_bad")] + \
+               [(n, C.c_int32) for n in ("b", "n_sigma", "n_leaves", "n_d")] + \
+               [("d_grad_scale", C.c_float), ("g_grad_scale", C.c_float)]
+
+
+TRAIN_STATS_N = 25                   # XMC_TRAIN_STATS_N
 
 _P, _I, _L, _F = C.c_void_p, C.c_int32, C.c_int64, C.c_float
 
@@ -177,6 +187,9 @@ SIGNATURES = {
     "xmc_bert_attention_long": [_P, _P, _P, _P, _P, _I, _I, _I, _P],
     "xmc_bert_sentence": [_P, _P, _P, _I, _I, _I, _P],
     "xmc_metrics_accum": [_P, _I, _P, _P, _P],
+    "xmc_segment_sumsq_ws_bytes": [_P, _I],
+    "xmc_segment_sumsq": [_P, _L, _P, _P, _I, _P, _P, _P, _L, _P],
+    "xmc_train_stats": [_P, _P],
 }
 
 # diagnostic probes: include/xmc_probe.h, libxmc_probe.so (csrc_probe/) -- outside the product ABI
@@ -190,7 +203,7 @@ PROBE_SIGNATURES = {
 }
 
 _INT64_RETURNS = ("xmc_conv2d_mx8_workspace_bytes", "xmc_conv2d_mx8_phase_in_workspace_bytes", "xmc_conv2d_workspace_bytes", "xmc_bn_stats_ws_floats", "xmc_cbn_bwd_sums_ws_floats",
-                  "xmc_conv2d_wgrad_workspace_bytes", "xmc_reduce_mid_ws_floats", "xmc_gemm_ws_floats")
+                  "xmc_conv2d_wgrad_workspace_bytes", "xmc_reduce_mid_ws_floats", "xmc_gemm_ws_floats", "xmc_segment_sumsq_ws_bytes")
 _lib = None
 
 

@@ -891,6 +891,28 @@ class HipOps:
         ptrs = (C.c_void_p * n)(*[v.data_ptr() for v in vals])
         check(self.lib.xmc_metrics_accum(ptrs, n, _p(sums), _p(info), self._stream()), "xmc_metrics_accum")
 
+    def segment_sumsq_ws_bytes(self, segs_host, nseg):
+        """bytes of workspace ``segment_sumsq`` needs for the HOST table ``segs_host`` (a ctypes int64 array of nseg (offset, length) pairs)"""
+        nbytes = self.lib.xmc_segment_sumsq_ws_bytes(segs_host, nseg)
+        check(min(nbytes, 0), "xmc_segment_sumsq_ws_bytes")
+        return nbytes
+
+    def segment_sumsq(self, x, segs, segs_host, sumsq, nonfinite, ws):
+        """per (offset, length) segment of the flat float32 buffer ``x``: float64 sum of squares -> sumsq, number of non-finite
+        elements -> nonfinite (int32).  ``segs``: (nseg, 2) int64 device table, ``segs_host``: its host copy (ctypes int64 array),
+        ``ws``: uint8 workspace of ``segment_sumsq_ws_bytes``.  Two launches on the current stream, no atomics (capturable)."""
+        nseg = segs.shape[0]
+        assert x.dtype == torch.float32 and x.is_contiguous() and segs.dtype == torch.int64 and segs.is_contiguous()
+        assert sumsq.dtype == torch.float64 and sumsq.numel() >= nseg and sumsq.is_contiguous()
+        assert nonfinite.dtype == torch.int32 and nonfinite.numel() >= nseg and nonfinite.is_contiguous()
+        assert len(segs_host) == 2 * nseg and ws.dtype == torch.uint8
+        check(self.lib.xmc_segment_sumsq(_p(x), x.numel(), _p(segs), segs_host, nseg, _p(sumsq), _p(nonfinite), _p(ws), ws.numel(),
+                                         self._stream()), "xmc_segment_sumsq")
+
+    def train_stats(self, args):
+        """one single-workgroup launch of xmc_train_stats on the current stream; ``args``: a filled ``_lib.TrainStatsArgs``"""
+        check(self.lib.xmc_train_stats(C.byref(args), self._stream()), "xmc_train_stats")
+
     def zeros_act(self, shape):
         """zero-filled tensor in the activation dtype (one memset)"""
         return torch.zeros(shape, dtype=self.dtype, device=self.device)

@@ -479,6 +479,18 @@ class JsonlWriter:
             f.write(json.dumps({"step": int(step), **{k: float(v) for k, v in scalars.items()}}) + "\n")
 
 
+def write_layer_stats(path, step, window):
+    """One line per scalar-writing boundary: ``{"step": s, "count": steps in the window, "leaves": {"d/<path>" | "g/<path>":
+    {"grad_norm_rms", "param_norm_rms", "nonfinite"}}}`` from ``TrainStatistics.read()`` -- per physical tensor of the arenas the
+    RMS over the window of the per-step gradient norm, of the parameter norm, and the non-finite gradient elements seen."""
+    import json
+    n = max(window["count"], 1)
+    leaves = {name: {"grad_norm_rms": (gsq / n) ** 0.5, "param_norm_rms": (psq / n) ** 0.5, "nonfinite": int(bad)}
+              for name, (gsq, psq, bad) in window["leaves"].items()}
+    with open(path, "a") as f:
+        f.write(json.dumps({"step": int(step), "count": int(window["count"]), "leaves": leaves}) + "\n")
+
+
 def write_image_grids(directory, step, image_dict):
     """Each ``(1, H, W, 3)`` float grid of ``generate_batch`` (values in [0, 1]) as ``<directory>/<name>_<step>.png``"""
     import os
@@ -554,6 +566,7 @@ def train(config, workdir, test_mode=False, *, datasets=None):
     use_graph = ops.device.type == "cuda" and xmc_net._OPS_FACTORY is None
     accumulator = MetricAccumulator(xmc_gan.METRIC_KEYS, ops)
     writer = JsonlWriter(os.path.join(workdir, "metrics.jsonl"))
+    statistics = additional_data.get("statistics")   # config.train_statistics: filled by train_g_d, read at the boundaries below
     graphed, window_start = None, initial_step
     n_split = config.d_step_per_g_step
     for step in range(initial_step, num_train_steps + 1):
@@ -575,12 +588,24 @@ def train(config, workdir, test_mode=False, *, datasets=None):
             continue
         sums, count, first_bad = accumulator.read()
         if first_bad:
+            where = ""
+            if statistics is not None:
+                bad = statistics.read()["first_bad"]
+                where = (f"; the first gradient that held a non-finite value was {bad[1]} at step {window_start + bad[0] - 1}"
+                         if bad else "; no gradient held a non-finite value")
             raise FloatingPointError(f"train: a training metric was not finite at step {window_start + first_bad - 1}; "
-                                     f"no checkpoint of that state is written (the newest one is {rotation.latest()})")
+                                     f"no checkpoint of that state is written (the newest one is {rotation.latest()}){where}")
         state = xmc_gan._flush(state)
         if write_scalars:
+            scalars = {k: sums[k] / count for k in accumulator.keys}
+            if statistics is not None:               # this replica's statistics (not averaged over replicas): window means
+                window = statistics.read()
+                if writes:
+                    scalars.update({f"stats/{k}": v / max(window["count"], 1) for k, v in window["sums"].items()})
+                    write_layer_stats(os.path.join(workdir, "layer_stats.jsonl"), step, window)
+                statistics.reset()
             if writes:
-                writer.write_scalars(step, {k: sums[k] / count for k in accumulator.keys})
+                writer.write_scalars(step, scalars)
             accumulator.reset()
             window_start = step + 1
             if writes:

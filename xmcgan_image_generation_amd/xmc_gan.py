@@ -75,6 +75,9 @@ def create_additional_data(config):
         params, batch_stats = pretrained_model_utils.get_pretrained_model(checkpoint_path=path)
         state = {"params": params, "batch_stats": batch_stats}
         additional_data.update({"image_model": pretrained_model_utils.ImageModel(state), "image_model_state": state})
+    if config.get("train_statistics", False):        # build-side: in-graph statistics of train_g_d (train_statistics.py)
+        from .train_statistics import TrainStatistics
+        additional_data["statistics"] = TrainStatistics()
     return additional_data
 
 
@@ -205,7 +208,9 @@ def _generator_forward(rng, config, state, batch, g, need_tape):
                      need_tape=need_tape)
 
 
-def _forward(rng, config, state, batch, g, d, need_g_tape, image_model=None, after_trunk=None, want_metrics=True):
+def _forward(rng, config, state, batch, g, d, need_g_tape, image_model=None, after_trunk=None, want_metrics=True, stats=None):
+    """``stats`` (a ``TrainStatistics``, train_g_d only): the discriminator forward also computes the heads' accuracy / entropy
+    pairs and hands its logits, losses and sigmas to it"""
     ops = g.ops
     cond = {k: batch[k] for k in ("sentence_embedding", "embedding", "max_len")}
     deferred = getattr(state, "pending", None) is not None
@@ -253,7 +258,10 @@ def _forward(rng, config, state, batch, g, d, need_g_tape, image_model=None, aft
     logit, loss_vec, new_sn, d_tape = d.forward(state.d_optimizer.target,
                                                 state.discriminator_state["spectral_norm_stats"], all_images,
                                                 cond, need_tape=True, fake_losses=need_g_tape, prepared=new_sn,
-                                                **({"after_trunk": after_trunk} if after_trunk is not None else {}))
+                                                **({"after_trunk": after_trunk} if after_trunk is not None else {}),
+                                                **({"want_stats": True} if stats is not None else {}))
+    if stats is not None:
+        stats.note_forward(logit, loss_vec, d.last_stats, d._sn_ctx[3])
     b = img.shape[0]
     hinge = ops.zeros((2,))
     dld, dlg = losses.hinge_loss(ops, logit, b, hinge[0:1], hinge[1:2])      # xmc_gan.py:144-145
@@ -269,13 +277,17 @@ def _forward(rng, config, state, batch, g, d, need_g_tape, image_model=None, aft
     return state, out, dld, dlg, g_tape, d_tape, new_g_stats, new_sn, pre
 
 
-def _apply_adam(ops, opt, config, lr, grad_scale, ema=None, fix_args=None, net=None):
+def _apply_adam(ops, opt, config, lr, grad_scale, ema=None, fix_args=None, net=None, stats=None):
     """flax.optim.Adam.apply_gradient (+ EMA).  ``fix_args`` (Discriminator.sn_fix_args()): the gradient through sigma of the
     spectrally-normalised weights rides in the optimiser kernel -- its scalar <G, W> is formed HERE, on the gradient the
     update consumes (after the replicas' exchange: the term is linear in G, and u, v, sigma are identical on every replica).
     ``net`` (the Generator / Discriminator that owns the arena; round 5, ops.fuse_prep): the update of its batched-preparation
-    weights also EMITS their prepared copies for the next forward pass (xmc_adam_wprep_tiles)."""
+    weights also EMITS their prepared copies for the next forward pass (xmc_adam_wprep_tiles).
+    ``stats`` = (TrainStatistics, "d" | "g") (train_g_d's own updates only): the per-tensor sums of squares of the gradient this
+    update consumes and of the parameters it is about to change, in front of it on this update's stream."""
     a = opt.arena
+    if stats is not None:
+        stats[0].leaf_pass(ops, stats[1], a, grad_scale)
     a.note_steps(1)
     decay = config.polyak_decay if ema is not None else 0.0
     if getattr(a, "first_write", False):
@@ -423,8 +435,11 @@ def train_g_d(rng, state, batch, generator, discriminator, config, additional_da
         d_arena.zero_grads()                 # (with a deferred D update the arena is still being exchanged: _forward)
     g_arena.zero_grads()
     image_model = additional_data["image_model"] if config.get("pretrained_image_contrastive", False) else None
+    stats = additional_data.get("statistics")        # (create_additional_data adds it for config.train_statistics)
+    if stats is not None:
+        stats.bind(ops, d_arena, g_arena)
     state, out, dld, dlg, g_tape, d_tape, new_g_stats, new_sn, pre = _forward(rng, config, state, batch, g, d,
-                                                                              need_g_tape=True, image_model=image_model)
+                                                                              need_g_tape=True, image_model=image_model, stats=stats)
     b = g_tape["b"]
     d_scale = g_scale = 1.0
     c_pre = None
@@ -488,7 +503,8 @@ def train_g_d(rng, state, batch, generator, discriminator, config, additional_da
             # reading D's parameters any more: it runs HERE, beside the generator's backward pass on the side stream (MFMA-bound),
             # instead of after the join
             ops.wait_event(d_part_done)
-            _apply_adam(ops, state.d_optimizer, config, config.d_lr, d_scale, fix_args=_fix_args(d), net=d)
+            _apply_adam(ops, state.d_optimizer, config, config.d_lr, d_scale, fix_args=_fix_args(d), net=d,
+                        stats=(stats, "d") if stats is not None else None)
             d_updated = True
         ops.join_side()
         if excl:
@@ -501,7 +517,7 @@ def train_g_d(rng, state, batch, generator, discriminator, config, additional_da
             grad_sync.wait("d")
             grad_sync.wait("g")
         return _finish_g_d(ops, state, config, out, c_pre, new_g_stats, new_sn, d_scale, g_scale, grad_sync, _fix_args(d),
-                           d_updated=d_updated, nets=(g, d))
+                           d_updated=d_updated, nets=(g, d), stats=stats)
     keep_async = getattr(ops, "wgrad_async", False)
     if grad_sync is not None and hasattr(ops, "wgrad_async"):
         ops.wgrad_async = True               # data-parallel schedule: weight gradients beside the dgrad chain
@@ -528,21 +544,26 @@ def train_g_d(rng, state, batch, generator, discriminator, config, additional_da
         g_scale = grad_sync.all_reduce(g_arena.grads, "g")
         grad_sync.wait("d")
         grad_sync.wait("g")
-    return _finish_g_d(ops, state, config, out, c_pre, new_g_stats, new_sn, d_scale, g_scale, grad_sync, _fix_args(d), nets=(g, d))
+    return _finish_g_d(ops, state, config, out, c_pre, new_g_stats, new_sn, d_scale, g_scale, grad_sync, _fix_args(d), nets=(g, d),
+                       stats=stats)
 
 
 def _finish_g_d(ops, state, config, out, c_pre, new_g_stats, new_sn, d_scale, g_scale, grad_sync, fix_args=None, d_updated=False,
-                nets=(None, None)):
+                nets=(None, None), stats=None):
     """Optimiser updates, EMA, new state and metrics of train_g_d (xmc_gan.py:170-190).  ``d_updated``: the caller already
-    applied D's update (beside the generator's backward pass)."""
+    applied D's update (beside the generator's backward pass).  ``stats``: the step's ``TrainStatistics`` or None."""
     if grad_sync is not None:
         grad_sync.wait("d")
     if not d_updated:
-        _apply_adam(ops, state.d_optimizer, config, config.d_lr, d_scale, fix_args=fix_args, net=nets[1])
+        _apply_adam(ops, state.d_optimizer, config, config.d_lr, d_scale, fix_args=fix_args, net=nets[1],
+                    stats=(stats, "d") if stats is not None else None)
     if grad_sync is not None:
         grad_sync.wait("g")
     ema = state.ema_buffer if config.get("ema", True) else None
-    _apply_adam(ops, state.g_optimizer, config, config.g_lr, g_scale, ema, net=nets[0])  # + EMA, xmc_gan.py:174-177
+    _apply_adam(ops, state.g_optimizer, config, config.g_lr, g_scale, ema, net=nets[0],      # + EMA, xmc_gan.py:174-177
+                stats=(stats, "g") if stats is not None else None)
+    if stats is not None:
+        stats.finish(ops)
     new_state = state.replace(step=state.step + 1,
                               generator_state={"batch_stats": new_g_stats},
                               discriminator_state={"spectral_norm_stats": new_sn})
