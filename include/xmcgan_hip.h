@@ -87,17 +87,19 @@ typedef struct {
     int32_t dtype;            /* dtype of x, w, mask, res (and y unless out_f32) */
     float alpha;              /* scale on the convolution result */
     float res_scale;
-    int32_t w_packed;         /* bit 0: w is in MFMA-fragment order (xmc_pack_conv_weight): bf16, cin % 32 == 0, ks == 3;
-                                 bit 4: w holds the 16-tap PHASE weights of xmc_phase_conv_weight -- only with ks == 3 and
+    int32_t w_packed;         /* 0: w is the plain prepared copy; else a sum of the XMC_CONV_* values below:
+                                 XMC_CONV_PACKED: w is in MFMA-fragment order (xmc_pack_conv_weight): bf16, cin % 32 == 0;
+                                 XMC_CONV_PHASE: w holds the 16-tap PHASE weights of xmc_phase_conv_weight -- only with ks == 3 and
                                  exactly one of ups / pool_out: the launch runs as four 2x2 convolutions on the low-resolution
                                  grid (16 instead of 36 multiply-adds per low-resolution pixel; `ups`: no res, `pool_out`: no mask);
-                                 bit 5: with bit 4 and `ups`: the one-phase-per-workgroup form (A/B hook of tools/);
-                                 bit 6: COMPACT pointwise launch (ks == 1, bf16, valid_h == valid_w = v > 0, no split-K): the
+                                 XMC_CONV_PHASE_PER_WG: with PHASE and `ups`: the one-phase-per-workgroup form (A/B hook of tools/);
+                                 XMC_CONV_COMPACT: compact pointwise launch (ks == 1, bf16, valid_h == valid_w = v > 0, no split-K): the
                                  workgroups cover only the v x v valid pixels of each ho x wo canvas (ResNet's 112/56/28/14/7
                                  maps on 128/64/32/16/8 canvases: 1.31x fewer pixels); margin pixels of y are NOT written --
                                  the caller keeps y in a buffer whose margins are zero once and stay zero;
-                                 bit 7: with bit 4 and `ups`: keep the 64-pixel x 128-cout tiles where the 128-pixel x 64-cout
-                                 ones would be chosen (A/B hook); bits 8-15: kernel A/B hooks of tools/ (0 = the shipped choice) */
+                                 XMC_CONV_NO_PX128: with PHASE and `ups`: keep the 64-pixel x 128-cout tiles where the 128-pixel x
+                                 64-cout ones would be chosen (A/B hook); XMC_CONV_NO_TILE96 .. XMC_CONV_PW_TILE_*: kernel A/B hooks
+                                 of tools/ (0 = the shipped choice) */
     int32_t pool_out;         /* y = avg_pool2x2(v) + res_scale * res, y and res at (ho/2, wo/2): fused pooling of
                                  DiscBlock / DiscOptimizedBlock (common.py:76-78,131); w_packed, wo >= 32, no mask */
     int32_t relu_out;         /* ReLU on the result (after the residual) */
@@ -109,6 +111,20 @@ typedef struct {
                                  scale commutes with the convolution: xmcgan/libml/layers.py:209-233) -- the prepared
                                  weights are then a pure cast of W and need not wait for the power iteration */
 } xmc_conv_desc;
+/* xmc_conv_desc.w_packed */
+#define XMC_CONV_PACKED 0x1
+#define XMC_CONV_PHASE 0x10
+#define XMC_CONV_PHASE_PER_WG 0x20
+#define XMC_CONV_COMPACT 0x40
+#define XMC_CONV_NO_PX128 0x80
+#define XMC_CONV_NO_TILE96 0x100          /* A/B: 128-cout tiles where the 96-cout ones would be chosen */
+#define XMC_CONV_FORCE_TILE96 0x200       /* A/B: 96-cout tiles for every cout % 96 == 0 */
+#define XMC_CONV_NO_TILE64 0x400          /* A/B: no 64-cout tiles on unsplit few-tile 3x3 launches */
+#define XMC_CONV_NO_TILE32 0x800          /* A/B: no 32-cout tiles for the <= 32-channel outputs */
+#define XMC_CONV_PW_VARIANT_SHIFT 12      /* A/B, two bits: pointwise kernel 1 <32,3>, 2 <64,3>, 3 <32,4>; 0 = the shipped choice */
+#define XMC_CONV_PW_VARIANT_MASK 0x3
+#define XMC_CONV_PW_TILE_SHIFT 14         /* A/B, two bits: pointwise pixel tile 1 = 256, 2 = 128; 0 = the shipped choice */
+#define XMC_CONV_PW_TILE_MASK 0x3
 
 int xmc_conv2d_nhwc(const xmc_conv_desc* d, const void* x, const void* w, const float* bias,
                     const void* mask, const void* res, void* y, void* stream);
@@ -118,7 +134,7 @@ int xmc_conv2d_nhwc(const xmc_conv_desc* d, const void* x, const void* w, const 
  * split; ws may then be NULL).  The buffer needs no initialisation; each split writes its own float32 slice and a
  * finishing kernel applies the epilogue.  xmc_conv2d_nhwc == xmc_conv2d_nhwc_ws(..., ws = NULL, ...). */
 int64_t xmc_conv2d_workspace_bytes(const xmc_conv_desc* d);
-/* 1 when a descriptor with w_packed bit 4 (16-tap phase weights) is inside the phase-decomposed kernels' domain, else 0 (the
+/* 1 when a descriptor with XMC_CONV_PHASE (16-tap phase weights) is inside the phase-decomposed kernels' domain, else 0 (the
  * launch would return XMC_EINVAL): lets the caller decide between the phase copies and the plain 3x3 copies of a layer */
 int xmc_conv2d_phase_supported(const xmc_conv_desc* d);
 int xmc_conv2d_nhwc_ws(const xmc_conv_desc* d, const void* x, const void* w, const float* bias,
@@ -140,7 +156,7 @@ int xmc_conv2d_nhwc_bits(const xmc_conv_desc* d, const void* x, const void* w, c
  * projection shortcut and the block's last 1x1, eval-mode BatchNorm folded into W = [W3 | Wp], bias = b3 + bp) by ONE launch: the
  * projection's output is never written and re-read as the residual, and the sub-sampling copy in front of it is gone.
  * d as for xmc_conv2d_nhwc with ks = 1, dtype = XMC_BF16, cin = channels of x, fragment-packed w (K = cin + cin2; cin, cin2 multiples of
- * 32), COMPACT (w_packed bits 0 and 6, valid_h == valid_w = v with 0 < v < hi: only the v x v corner of every canvas is walked, the
+ * 32), COMPACT (w_packed = XMC_CONV_PACKED | XMC_CONV_COMPACT, valid_h == valid_w = v with 0 < v < hi: only the v x v corner of every canvas is walked, the
  * margins of y are not written); relu_out, mask_after_res honoured; no ups / res_ups / pool_out / relu_in / split-K.  mask / mask_bits /
  * res (each may be NULL) and y_bits (may be NULL; cout % 16 == 0) as in xmc_conv2d_nhwc_bits.
  * stride2 = 1 or 2: x2' as above.  stride2 = -2: the ADJOINT sampling -- x2' pixel (n, y, x) = x2[n, y / 2, x / 2, :] where y and x are both
@@ -168,7 +184,7 @@ int xmc_conv2d_pw_dual(const xmc_conv_desc* d, const void* x, const void* x2, in
  *   enables split-K on few-tile layers.  y8 (may be NULL; needs bf16 output, cout % 64 == 0 and a launch without
  *   split-K): the epilogue also writes y as packets for the NEXT convolution, y8_relu = that convolution's relu_in --
  *   byte for byte what xmc_mx8_quantize(y, relu) would write, without the extra pass.
- * The "out" PHASE form on MX-fp8 operands (ABI 24): d->w_packed = 1 | 16 with d->ups = 1 runs conv3x3(nearest_upsample2(x)) as four
+ * The "out" PHASE form on MX-fp8 operands (ABI 24): d->w_packed = XMC_CONV_PACKED | XMC_CONV_PHASE with d->ups = 1 runs conv3x3(nearest_upsample2(x)) as four
  *   2x2 convolutions on the low-resolution grid, y[2i+a][2j+b] = sum_{tu,tv} E_ab[tu][tv] x[i+a-1+tu][j+b-1+tv] (16 instead of 36
  *   block-scaled products per low-resolution pixel); x8 = the packets of the LOW-resolution tensor, w8 / wscale = the taps = 16
  *   output of xmc_mx8_pack_conv_weight.  Replaces, when config.conv_fp8_phase is set, the generator blocks' first convolution
@@ -178,11 +194,11 @@ int xmc_conv2d_pw_dual(const xmc_conv_desc* d, const void* x, const void* x2, in
  *   relu_in = res_ups = mask_after_res = valid_* = 0; res must be NULL.  bias, alpha, alpha_dev, mask, mask_bits, y_bits,
  *   relu_out, out_f32, y8 and the split-K workspace as for the 3x3 form (xmc_conv2d_mx8_workspace_bytes answers for these
  *   descriptors too).  Outside the domain the launch returns XMC_EINVAL; it never runs another kernel.
- * The "in" PHASE form on MX-fp8 operands (ABI 25; entry points of their own -- on xmc_conv2d_mx8 a pool_out descriptor with bit 4
+ * The "in" PHASE form on MX-fp8 operands (ABI 25; entry points of their own -- on xmc_conv2d_mx8 a pool_out descriptor with XMC_CONV_PHASE
  *   stays XMC_EINVAL): xmc_conv2d_mx8_phase_in[_bits] runs avg_pool2(conv3x3(x)) as four 2x2 convolutions on the low-resolution
  *   OUTPUT grid, decomposed by the parity (a, b) of the input pixel: y[i][j] = 1/4 sum_{a,b} sum_{tu,tv} F_ab[tu][tv]
  *   x[2(i+tu)-a][2(j+tv)-b] (16 instead of 36 block-scaled products per output pixel; every parity gathers whole 80-byte packets at
- *   pixel stride 2).  d: hi / wi = the INPUT map, ups = 0, pool_out = 1, w_packed = 1 | 16; x8 = the packets of the input tensor; w8 /
+ *   pixel stride 2).  d: hi / wi = the INPUT map, ups = 0, pool_out = 1, w_packed = XMC_CONV_PACKED | XMC_CONV_PHASE; x8 = the packets of the input tensor; w8 /
  *   wscale = the taps = 16 output of xmc_mx8_pack_conv_weight on an "in"-order phase copy (xmc_phase_conv_weight / xmc_wprep_batched:
  *   tap = (2a + b) * 4 + tu * 2 + tv).  Replaces, when config.conv_fp8_phase_in is set, the second convolution of the down-sampling
  *   discriminator blocks (xmcgan/nets/common.py:76-78) and the data gradient of the generator blocks' first convolution (the
@@ -199,7 +215,7 @@ int xmc_mx8_quantize(const void* x, void* x8, int64_t pixels, int32_t c, int32_t
 int xmc_mx8_pack_conv_weight(const void* w_packed, void* w8, void* wscale, int32_t rows, int32_t taps, int32_t k,
                              void* stream);
 int64_t xmc_conv2d_mx8_workspace_bytes(const xmc_conv_desc* d);
-/* 1 when a descriptor with w_packed bits 0 and 4 is inside the MX-fp8 "out" phase kernel's domain, else 0 */
+/* 1 when a descriptor with XMC_CONV_PACKED | XMC_CONV_PHASE is inside the MX-fp8 "out" phase kernel's domain, else 0 */
 int xmc_conv2d_mx8_phase_supported(const xmc_conv_desc* d);
 /* 1 when the descriptor is inside the MX-fp8 "in" phase kernel's domain, else 0; its split-K workspace (0: none) */
 int xmc_conv2d_mx8_phase_in_supported(const xmc_conv_desc* d);
@@ -232,15 +248,27 @@ typedef struct {
     int32_t x_ups, x_relu;
     int32_t dy_ups;           /* dy is (n, ho/2, wo/2, cout), nearest-upsampled on load */
     int32_t dtype;            /* dtype of x and dy */
-    int32_t variant;          /* bits 0-3, kernel choice: 0 = generic split-K kernel only (bring-up / float32),
-                                 1 = auto (LDS-DMA kernel, else register-staged patch kernel, else generic),
-                                 2 = as 1 without the LDS-DMA kernel (A/B benchmarks);
+    int32_t variant;          /* a sum of the XMC_WGRAD_* fields below.  XMC_WGRAD_KERNEL_MASK, kernel choice: 0 = generic split-K
+                                 kernel only (bring-up / float32), 1 = auto (phase-decomposed kernel, else LDS-DMA kernel, else
+                                 register-staged patch kernel, else generic), 2 = as 1 without the phase and LDS-DMA kernels (A/B);
                                  XMC_WGRAD_OVERWRITE: dw / db = alpha * (...) instead of += -- the FIRST write of a gradient
                                  nobody zeroed (the optimiser then need not clear what it consumed, and the reducing pass
-                                 reads no old value); needs the workspace of xmc_conv2d_wgrad_ws for split launches */
+                                 reads no old value); needs the workspace of xmc_conv2d_wgrad_ws for split launches;
+                                 every other field: A/B hooks of tools/ (0 = the shipped choice) */
     float alpha;
 } xmc_wgrad_desc;
+/* xmc_wgrad_desc.variant */
+#define XMC_WGRAD_KERNEL_MASK 0xf
+#define XMC_WGRAD_TUNE_SHIFT 4            /* LDS-DMA kernel, four bits: bit 0 launch order, bits 1-3 workgroup target */
+#define XMC_WGRAD_TUNE_MASK 0xf
+#define XMC_WGRAD_PHASE_TARGET_SHIFT 5    /* phase kernel, three bits: index of its workgroup target -- OVERLAPS the tune field's */
+#define XMC_WGRAD_PHASE_TARGET_MASK 0x7   /* upper three bits (one sweep variable of tools/ drives either kernel) */
+#define XMC_WGRAD_NO_PHASE 0x100          /* no phase-decomposed kernel */
+#define XMC_WGRAD_FORCE_SHIFT 9           /* 1x1 LDS-DMA kernel, two bits: force 1 / 2 / 4 cin blocks per workgroup */
+#define XMC_WGRAD_FORCE_MASK 0x3
+#define XMC_WGRAD_NO_C96 0x800            /* no 96-cout tiles in the LDS-DMA kernel */
 #define XMC_WGRAD_OVERWRITE 0x1000
+#define XMC_WGRAD_NST3 0x2000             /* three-stage ring on the 4 x 4 maps too */
 
 /* db (may be NULL): the bias gradient of the same convolution, db[cout] += alpha * sum_p dy'(p, cout),
  * fused into the weight-gradient kernel. */
@@ -265,7 +293,7 @@ int xmc_prep_conv_weight(const float* w, const float* inv_sigma, void* w_fwd, vo
 /* Prepared bf16 weights [cout][taps][cin] (forward or dgrad copy) -> MFMA-fragment order
  *   [ceil(cout/32)][cin/32][tap][k16 half][lane 0..63][8]   lane = (k8 half) * 32 + cout % 32
  * (ceil(cout/32) * 32 * taps * cin elements; rows >= cout are zero) consumed by xmc_conv2d_nhwc with
- * desc.w_packed = 1: every MFMA A operand is then one coalesced 1 KiB load, no LDS staging of weights. */
+ * desc.w_packed = XMC_CONV_PACKED: every MFMA A operand is then one coalesced 1 KiB load, no LDS staging of weights. */
 int xmc_pack_conv_weight(const void* w, void* out, int32_t cout, int32_t taps, int32_t cin, void* stream);
 
 /* Phase weights of a 3x3 layer that sits next to a 2x resampling (the generator blocks' conv3x3(upsample(.)),
@@ -280,7 +308,7 @@ int xmc_pack_conv_weight(const void* w, void* out, int32_t cout, int32_t taps, i
  *               -- xmcgan/utils/resnet_v1.py:70): single taps instead of sums (7 of the 16 entries are zero); w_fwd for a
  *               pool_out launch with alpha = 4 (y at half the resolution), w_dgrad for the ups launch that computes the adjoint.
  * Both outputs: fragment order with 16 taps, rows * 16 * k bf16 elements (cout % 32 == 0, cin % 32 == 0); pass them
- * with desc.w_packed = 1 | 16.  Either may be NULL. */
+ * with desc.w_packed = XMC_CONV_PACKED | XMC_CONV_PHASE.  Either may be NULL. */
 int xmc_phase_conv_weight(const float* w, const float* inv_sigma, void* w_fwd, void* w_dgrad, int32_t cout, int32_t cin,
                           int32_t fwd_mode, void* stream);
 

@@ -304,7 +304,8 @@ def test_conv_wgrad_96_cout_tiles_equal_128_cout_tiles_and_first_write(case):
     x, _ = _rnd((n, h, h, cin), torch.bfloat16, g)
     dy, _ = _rnd((n, h, h, cout), torch.bfloat16, g)
     outs = []
-    for off in (0, 0x800):
+    from xmcgan_image_generation_amd._lib import XMC_WGRAD_NO_C96
+    for off in (0, XMC_WGRAD_NO_C96):
         ops.wgrad_variant = 1 | off
         dw = torch.zeros((cout, 9, cin), device="cuda")
         db = torch.zeros((cout,), device="cuda")
@@ -1227,3 +1228,51 @@ def test_word_loss_all_equal_features_is_two_ln_b():
     loss = torch.zeros(1, device="cuda")
     A.word_loss_fwd(ops, feat, A.normalize_words(ops, words), ml, loss)
     assert abs(float(loss) - 2 * math.log(b)) < 1e-4
+
+
+def test_conv_routes():
+    """one small launch per route of HipOps._conv_route: the route it names and the last_conv_* flags after the launch (parity of
+    these launches: test_conv_stream_packed, test_conv_pointwise_*, test_conv_phase, test_conv_stride2_phase, tests/test_gpu_mx8*.py)"""
+    from xmcgan_image_generation_amd.ops import HipOps
+    dtype = torch.bfloat16
+    g = torch.Generator().manual_seed(77)
+    seen = set()
+
+    def run(ops, want, x, w, *, mx8_phase=False, mx8_phase_in=False, shape=None, **kw):
+        before = (ops.mx8_phase_launches, ops.mx8_phase_in_launches)
+        y = ops.conv(x, w, None, **kw)
+        torch.cuda.synchronize()
+        assert ops.last_conv_route == want and want in HipOps.ROUTES, (ops.last_conv_route, want)
+        assert ops.last_conv_phase == ("phase" in want)
+        assert (ops.last_conv_mx8_phase, ops.last_conv_mx8_phase_in) == (mx8_phase, mx8_phase_in)
+        assert (ops.mx8_phase_launches, ops.mx8_phase_in_launches) == (before[0] + int(mx8_phase), before[1] + int(mx8_phase_in))
+        assert tuple(y.shape) == shape and bool(torch.isfinite(y.float()).all())
+        seen.add(want)
+
+    def weights(ops, cout, taps, cin, phase=None):
+        return ops.prep_conv_weight((torch.randn((cout, taps, cin), generator=g) * 0.05).cuda(), None, True, phase=phase)
+
+    x16, _ = _rnd((2, 16, 16, 64), dtype, g)         # n = 2, 16 x 16, 64 -> 64
+    x4, _ = _rnd((3, 4, 4, 64), dtype, g)            # n = 3, 4 x 4, 64 -> 128: a tile holds several images
+    x8, _ = _rnd((2, 8, 8, 64), dtype, g)            # 8 x 8 -> 4 x 4 for the MX "in" form
+    run(_ops(dtype), "plain", x16, weights(_ops(dtype), 64, 9, 64)[0], ks=3, shape=(2, 16, 16, 64))
+    ops = HipOps(dtype=dtype)
+    run(ops, "stream3", x16, weights(ops, 64, 9, 64)[0], ks=3, shape=(2, 16, 16, 64))
+    run(ops, "stream3", x4, weights(ops, 128, 9, 64)[0], ks=3, shape=(3, 4, 4, 128))
+    run(ops, "pointwise", x16, weights(ops, 64, 1, 64)[0], ks=1, shape=(2, 16, 16, 64))
+    x2, _ = _rnd((2, 16, 16, 32), dtype, g)
+    run(ops, "pw_dual", x16, weights(ops, 64, 1, 96)[0], ks=1, x2=x2, valid=14, compact=True, shape=(2, 16, 16, 64),
+        out=torch.zeros((2, 16, 16, 64), dtype=dtype, device="cuda"))
+    run(ops, "phase_out", x16, weights(ops, 64, 9, 64, "ups")[0], ks=3, ups=True, shape=(2, 32, 32, 64))
+    run(ops, "phase_out", x4, weights(ops, 128, 9, 64, "ups")[0], ks=3, ups=True, shape=(3, 8, 8, 128))
+    run(ops, "phase_in", x16, weights(ops, 64, 9, 64, "pool")[0], ks=3, pool_out=True, shape=(2, 8, 8, 64))
+    run(ops, "phase_s2", x16, weights(ops, 64, 9, 64, "s2")[0], ks=3, stride2=True, shape=(2, 8, 8, 64))
+    ops.fp8 = True                                   # the MX-fp8 mode: the 3x3 kernel; the phase sites stay bf16 until their switches are on
+    run(ops, "mx8", x16, weights(ops, 64, 9, 64)[0], ks=3, shape=(2, 16, 16, 64))
+    run(ops, "stream3", x4, weights(ops, 128, 9, 64)[0], ks=3, shape=(3, 4, 4, 128))      # 4 x 4 maps: the MX patch does not fit
+    run(ops, "phase_out", x16, weights(ops, 64, 9, 64, "ups")[0], ks=3, ups=True, shape=(2, 32, 32, 64))
+    ops.fp8_phase_mx = ops.fp8_phase_in_mx = True
+    run(ops, "mx8_phase_out", x16, weights(ops, 64, 9, 64, "ups")[0], ks=3, ups=True, mx8_phase=True, shape=(2, 32, 32, 64))
+    run(ops, "mx8_phase_out", x4, weights(ops, 128, 9, 64, "ups")[0], ks=3, ups=True, mx8_phase=True, shape=(3, 8, 8, 128))
+    run(ops, "mx8_phase_in", x8, weights(ops, 64, 9, 64, "pool")[0], ks=3, pool_out=True, mx8_phase_in=True, shape=(2, 4, 4, 64))
+    assert seen == set(HipOps.ROUTES)

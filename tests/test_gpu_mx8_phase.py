@@ -176,8 +176,9 @@ def test_conv_phase_mx8_exact_on_lossless_operands(h, n, k, rows, form, split_k,
     check_against_float64((h, n, k, rows, form, split_k, opts), y, x.double(), wl, opts.get("bands"), **ref_kw)
 
 
-def _desc(ops, n, h, k, rows, flags=1 | 16, pool_out=0):
-    from xmcgan_image_generation_amd._lib import ConvDesc
+def _desc(ops, n, h, k, rows, flags=None, pool_out=0):
+    from xmcgan_image_generation_amd._lib import XMC_CONV_PACKED, XMC_CONV_PHASE, ConvDesc
+    flags = XMC_CONV_PACKED | XMC_CONV_PHASE if flags is None else flags
     return ConvDesc(n, h, h, k, rows, 3, 1, 0, 0, 0, ops.code, 1.0, 1.0, flags, pool_out, 0, 0, 0, 0, None)
 
 

@@ -121,8 +121,8 @@ def check_against_float64(tag, y, x64, wl, bands, alpha=1.0, bias=None, res=None
 
 
 def _desc(ops, n, hin, k, rows):
-    from xmcgan_image_generation_amd._lib import ConvDesc
-    return ConvDesc(n, hin, hin, k, rows, 3, 0, 0, 0, 0, ops.code, 1.0, 1.0, 1 | 16, 1, 0, 0, 0, 0, None)
+    from xmcgan_image_generation_amd._lib import XMC_CONV_PACKED, XMC_CONV_PHASE, ConvDesc
+    return ConvDesc(n, hin, hin, k, rows, 3, 0, 0, 0, 0, ops.code, 1.0, 1.0, XMC_CONV_PACKED | XMC_CONV_PHASE, 1, 0, 0, 0, 0, None)
 
 
 # OUTPUT grid, n, reduction length K, rows, form, split-K, options.  Images per tile: 16 at 4^2, 4 at 8^2, 1 from 16^2 on.

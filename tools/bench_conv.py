@@ -8,6 +8,7 @@ import sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch  # noqa: E402
 
+from xmcgan_image_generation_amd import _lib  # noqa: E402
 from xmcgan_image_generation_amd.ops import HipOps  # noqa: E402
 
 # (tag, n, h_in, cin, cout, ks, ups)
@@ -60,9 +61,9 @@ def main():
     ap.add_argument("--all96", action="store_true", help="with --tile-ab: 96-cout tiles for EVERY Cout % 96 == 0 layer in the second column")
     ap.add_argument("--fp8", action="store_true", help="MX-fp8 3x3 convolution (fwd + dgrad) next to the bf16 kernel")
     ap.add_argument("--wgrad-tunes", default=None,
-                    help="comma list of LDS-DMA wgrad tuning values (xmc_wgrad_desc.variant >> 4): wgrad only, one column each")
+                    help="comma list of LDS-DMA wgrad tuning values (the XMC_WGRAD_TUNE_* field of xmc_wgrad_desc.variant): wgrad only, one column each")
     ap.add_argument("--wgrad-raw", action="store_true", help="--wgrad-tunes values are RAW xmc_wgrad_desc.variant values (e.g. 1,2049: "
-                    "the launcher's choice vs bit 11 = no 96-cout tiles); x_relu off")
+                    "the launcher's choice vs XMC_WGRAD_NO_C96); x_relu off")
     args = ap.parse_args()
     dt = torch.bfloat16 if args.dtype == "bf16" else torch.float32
     ops = HipOps(dtype=dt, stream_conv=args.packed)
@@ -94,7 +95,7 @@ def main():
         return
     if args.fp8:
         import ctypes as C
-        from xmcgan_image_generation_amd._lib import ConvDesc, XMC_BF16
+        from xmcgan_image_generation_amd._lib import ConvDesc, XMC_BF16, XMC_CONV_PACKED
         print(f"{'layer':26s} {'GF':>7s} | {'bf16 fwd':>9s} {'TF/s':>6s} | {'quant ms':>8s} | {'mx8 conv':>8s} {'TF/s':>6s} | {'mx8 total':>9s} {'x bf16':>6s} || "
               f"{'bf16 dgr':>9s} | {'quant':>6s} | {'mx8 conv':>8s} {'TF/s':>6s} | {'x bf16':>6s}")
         tot = [0.0] * 8
@@ -115,7 +116,7 @@ def main():
                 x8 = ops.quantize_mx8(inp)
                 nn, hh, _, cc = inp.shape
                 y = torch.empty((nn, 2 * hh if u else hh, 2 * hh if u else hh, wt.cout), dtype=dt, device="cuda")
-                d = ConvDesc(nn, hh, hh, cc, wt.cout, 3, int(u), 0, 0, 0, XMC_BF16, 1.0, 1.0, 1, 0, 0, 0, 0, 0)
+                d = ConvDesc(nn, hh, hh, cc, wt.cout, 3, int(u), 0, 0, 0, XMC_BF16, 1.0, 1.0, XMC_CONV_PACKED, 0, 0, 0, 0, 0)
                 wsb = ops.lib.xmc_conv2d_mx8_workspace_bytes(C.byref(d))
                 ws = torch.empty((max(wsb, 4) // 4,), dtype=torch.float32, device="cuda")
                 p_ = lambda t: C.c_void_p(t.data_ptr())
@@ -158,7 +159,7 @@ def main():
             rounds = 4
             for r in range(rounds + 1):
                 for i, t in enumerate(tunes):
-                    ops.wgrad_variant = t if args.wgrad_raw else 1 | (t << 4)
+                    ops.wgrad_variant = t if args.wgrad_raw else 1 | (t << _lib.XMC_WGRAD_TUNE_SHIFT)
                     tw = timeit(lambda: ops.conv_wgrad(x, dy, dw, db, ks=ks, x_ups=ups, x_relu=not args.wgrad_raw), args.iters)
                     if r > 0:                     # round 0 = warm-up
                         acc[i] += tw / rounds

@@ -2,6 +2,7 @@
 usage (GPU box): PYTHONPATH=. python tools/bench_wgrad_1x1.py"""
 import os
 import torch
+from xmcgan_image_generation_amd._lib import XMC_WGRAD_FORCE_SHIFT
 from xmcgan_image_generation_amd.ops import HipOps
 
 ops = HipOps(torch.bfloat16)
@@ -17,7 +18,7 @@ for (n, h, cin, cout) in SHAPES:
     best = {}
     for r in range(4):
         for cb in (1, 2, 3):
-            ops.wgrad_variant = base | (cb << 9)
+            ops.wgrad_variant = base | (cb << XMC_WGRAD_FORCE_SHIFT)
             for _ in range(2):
                 ops.conv_wgrad(x, dy, dw, db, ks=1, sync=True)
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)

@@ -15,7 +15,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=30)
     a = ap.parse_args()
-    from xmcgan_image_generation_amd._lib import XMC_BF16, ConvDesc
+    from xmcgan_image_generation_amd._lib import XMC_BF16, XMC_CONV_PACKED, ConvDesc
     from xmcgan_image_generation_amd.ops import HipOps
     ops = HipOps(dtype=torch.bfloat16)
     g = torch.Generator().manual_seed(0)
@@ -46,7 +46,7 @@ def main():
         w = (torch.randn((cout, 9, cin), generator=g) / (9 * cin) ** 0.5).cuda()
         wf, _ = ops.prep_conv_weight(w)
         ho = 2 * h if ups else h
-        d = ConvDesc(n, h, h, cin, cout, 3, int(ups), 0, 0, 0, XMC_BF16, 1.0, 1.0, 1, 0, 0, 0, 0, 0)
+        d = ConvDesc(n, h, h, cin, cout, 3, int(ups), 0, 0, 0, XMC_BF16, 1.0, 1.0, XMC_CONV_PACKED, 0, 0, 0, 0, 0)
         wsb = ops.lib.xmc_conv2d_mx8_workspace_bytes(C.byref(d))
 
         def run_all():

@@ -20,6 +20,15 @@ PROBE_LIB_PATH = os.path.join(_HERE, "libxmc_probe.so")
 XMC_F32, XMC_BF16 = 0, 1
 ABI_VERSION = 30
 
+# xmc_conv_desc.w_packed and xmc_wgrad_desc.variant: the names of include/xmcgan_hip.h (tests/test_conv_geometry.py keeps them equal)
+XMC_CONV_PACKED, XMC_CONV_PHASE, XMC_CONV_PHASE_PER_WG, XMC_CONV_COMPACT, XMC_CONV_NO_PX128 = 0x1, 0x10, 0x20, 0x40, 0x80
+XMC_CONV_NO_TILE96, XMC_CONV_FORCE_TILE96, XMC_CONV_NO_TILE64, XMC_CONV_NO_TILE32 = 0x100, 0x200, 0x400, 0x800
+XMC_CONV_PW_VARIANT_SHIFT, XMC_CONV_PW_VARIANT_MASK, XMC_CONV_PW_TILE_SHIFT, XMC_CONV_PW_TILE_MASK = 12, 0x3, 14, 0x3
+XMC_WGRAD_KERNEL_MASK, XMC_WGRAD_TUNE_SHIFT, XMC_WGRAD_TUNE_MASK = 0xf, 4, 0xf
+XMC_WGRAD_PHASE_TARGET_SHIFT, XMC_WGRAD_PHASE_TARGET_MASK = 5, 0x7          # overlaps the tune field (see the header)
+XMC_WGRAD_NO_PHASE, XMC_WGRAD_FORCE_SHIFT, XMC_WGRAD_FORCE_MASK = 0x100, 9, 0x3
+XMC_WGRAD_NO_C96, XMC_WGRAD_OVERWRITE, XMC_WGRAD_NST3 = 0x800, 0x1000, 0x2000
+
 
 class ConvDesc(C.Structure):
     _fields_ = [(n, C.c_int32) for n in

@@ -23,6 +23,7 @@
 #include <type_traits>
 
 #include "common.h"
+#include "conv_plan.h"
 
 namespace {
 
@@ -109,7 +110,7 @@ __global__ __launch_bounds__(NW * 64, ((WCB == 3 && WPB == 1) || (NW == 3 && WPB
     const int ty = rest & ((1 << p.log2_ty) - 1);
     const int img0 = (rest >> p.log2_ty) << p.log2_imgs;
     const int y0 = ty << p.log2_rt, x0 = tx << p.log2_wt;
-    // COMPACT 3x3 launches (w_packed bit 6 + valid_h, round 6): a tile that lies entirely in the canvas margin -- rows 56 .. 63 of the
+    // COMPACT 3x3 launches (XMC_CONV_COMPACT + valid_h, round 6): a tile that lies entirely in the canvas margin -- rows 56 .. 63 of the
     // frozen ResNet-50's 64^2 canvases: two of sixteen row tiles -- is not computed; nobody reads those pixels (the pointwise
     // consumers are compact themselves)
     if (p.vh && (y0 >= p.vh || x0 >= p.vh)) return;
@@ -1382,77 +1383,61 @@ extern "C" int xmc_phase_conv_weight(const float* w, const float* inv_sigma, voi
     XMC_LAUNCH_RET();
 }
 
-// Geometry of the phase-decomposed launch (w_packed bit 4: `w` holds the 16-tap phase weights): the 2x2 convolutions run
+// Geometry of the phase-decomposed launch (XMC_CONV_PHASE: `w` holds the 16-tap phase weights): the 2x2 convolutions run
 // on the LOW-resolution grid -- the input grid of an `ups` launch, the pooled output grid of a `pool_out` launch.
-struct PhaseGeom { int mode, hv, wv, wt, rt, imgs, pp; long long tiles_m; bool tile96; int tiles_n, ksplit; bool waves4, px128; };
+struct PhaseGeom { int mode, hv, wv; XmcTilePlan plan; bool tile96; int tiles_n, ksplit; bool waves4, px128; };
 static bool phase_geom(const xmc_conv_desc* d, PhaseGeom* g) {
-    if (!((d->w_packed >> 4) & 1) || d->dtype != XMC_BF16 || d->ks != 3 || (d->cin % 32) != 0 || (d->cout % 4) != 0) return false;
+    if (!(d->w_packed & XMC_CONV_PHASE) || d->dtype != XMC_BF16 || d->ks != 3 || (d->cin % 32) != 0 || (d->cout % 4) != 0) return false;
     if ((d->ups != 0) == (d->pool_out != 0)) return false;
     if (d->res_ups || d->mask_after_res || d->valid_h) return false;
     g->mode = d->ups ? 0 : 1;
     g->hv = d->ups ? d->hi : d->hi / 2; g->wv = d->ups ? d->wi : d->wi / 2;
     if (g->hv < 2 || g->wv < 2 || ilog2_exact(g->hv) < 0 || ilog2_exact(g->wv) < 0) return false;
     if (!d->ups && ((d->hi & 1) || (d->wi & 1))) return false;
-    // "out" form: the four phases as the four waves of a 64-pixel tile (conv_phase4_kernel) unless bit 5 of w_packed asks
+    // "out" form: the four phases as the four waves of a 64-pixel tile (conv_phase4_kernel) unless XMC_CONV_PHASE_PER_WG asks
     // for the phase-per-workgroup form (A/B runs)
-    g->waves4 = g->mode == 0 && !((d->w_packed >> 5) & 1);
+    g->waves4 = g->mode == 0 && !(d->w_packed & XMC_CONV_PHASE_PER_WG);
     // 128-pixel x 64-cout tiles of the phases-as-waves form (conv_phase4_kernel<2, 4>: half the weight traffic per MFMA) where
-    // the patch of a 16 x 8 pixel tile fits the three staging vectors per thread; w_packed bit 7: off (A/B)
-    g->px128 = g->waves4 && !((d->w_packed >> 7) & 1) && (d->cout % 64) == 0 && g->wv >= 16 && g->hv >= 8;
-    const int tile_px = g->px128 ? 128 : g->waves4 ? 64 : SBM;
-    g->wt = g->waves4 ? (g->wv < 16 ? g->wv : 16) : (g->wv < 64 ? g->wv : 64);
-    g->rt = tile_px / g->wt; if (g->rt > g->hv) g->rt = g->hv;
-    g->imgs = tile_px / (g->wt * g->rt);
-    g->pp = g->waves4 ? g->imgs * (g->rt + 2) * (g->wt + 2) : g->imgs * (g->rt + 1) * (g->wt + 1);
-    if (g->pp * 4 > (g->waves4 ? NV4 : NVP) * 256) return false;
-    g->tiles_m = (long long)((d->n + g->imgs - 1) / g->imgs) * (g->wv / g->wt) * (g->hv / g->rt);
+    // the patch of a 16 x 8 pixel tile fits the three staging vectors per thread; XMC_CONV_NO_PX128: off (A/B)
+    g->px128 = g->waves4 && !(d->w_packed & XMC_CONV_NO_PX128) && (d->cout % 64) == 0 && g->wv >= 16 && g->hv >= 8;
+    // tiles at most 16 (phases as waves) / 64 pixels wide; the patch is the tile plus a two- / one-pixel margin
+    g->plan = xmc_tile_plan(d->n, g->hv, g->wv, g->px128 ? 128 : g->waves4 ? 64 : SBM, g->waves4 ? 16 : 64, g->waves4 ? 2 : 1, 4,
+                            (g->waves4 ? NV4 : NVP) * 256);
+    if (!g->plan.fits) return false;
     g->tile96 = !g->px128 && (d->cout % 96) == 0 && (d->cout % 128) != 0 && d->cout <= 192;
     g->tiles_n = g->px128 ? d->cout / 64 : g->tile96 ? d->cout / 96 : (d->cout + 127) / 128;
-    const long long wgs = g->tiles_m * g->tiles_n * (g->mode == 0 && !g->waves4 ? 4 : 1);
-    const int nchunks = d->cin / 32;
-    int ks = 1;
-    const int target = xmc_internal_tuning(XMC_TUNE_KSPLIT_TARGET_PHASE);
-    if (wgs < 384 && nchunks >= 16) {
-        ks = (int)((target + wgs / 2) / wgs);
-        if (ks > nchunks / 4) ks = nchunks / 4;
-        if (ks < 2) ks = 1;
-    }
-    g->ksplit = ks;
+    const long long wgs = g->plan.tiles_m * g->tiles_n * (g->mode == 0 && !g->waves4 ? 4 : 1);
+    g->ksplit = xmc_ksplit_for(wgs, d->cin / 32, 384, 16, xmc_internal_tuning(XMC_TUNE_KSPLIT_TARGET_PHASE), 4);
+    return true;
+}
+
+// What every launcher of this file puts into SArgs first: operands, shapes, scales and the byte extents of x and w (`taps` filter
+// taps over `k` reduction channels).  false: an operand is too large or misaligned.
+static bool stream_args(SArgs* a, const xmc_conv_desc* d, int ho, int wo, int taps, int k, const void* x, const void* w,
+                        const float* bias, const void* mask, const void* res, void* y) {
+    a->x = x; a->w = w; a->bias = bias; a->mask = mask; a->res = res; a->y = y;
+    a->N = d->n; a->Hi = d->hi; a->Wi = d->wi; a->Cin = d->cin; a->Cout = d->cout; a->Ho = ho; a->Wo = wo;
+    a->relu_in = d->relu_in; a->out_f32 = d->out_f32; a->relu_out = d->relu_out; a->mask_after = d->mask_after_res;
+    a->alpha = d->alpha; a->res_scale = d->res_scale; a->alpha_dev = d->alpha_dev;
+    a->nchunks = a->Cin / 32;
+    const long long xb = (long long)a->N * a->Hi * a->Wi * a->Cin * 2, wb = (long long)((a->Cout + 31) / 32) * 32 * taps * k * 2;
+    if (!xmc_extents_ok((long long)a->N * ho * wo, {xb, wb}, {x, w, y})) return false;
+    a->x_bytes = (unsigned)xb; a->w_bytes = (unsigned)wb;
     return true;
 }
 
 static int conv2d_phase(const xmc_conv_desc* d, const PhaseGeom& g, const void* x, const void* w, const float* bias,
                         const void* mask, const void* res, void* y, void* ws, const void* mask_bits, void* y_bits, void* stream) {
     SArgs a{};
-    a.x = x; a.w = w; a.bias = bias; a.mask = mask; a.res = res; a.y = y;
-    a.N = d->n; a.Hi = d->hi; a.Wi = d->wi; a.Cin = d->cin; a.Cout = d->cout;
-    a.Ho = g.mode == 0 ? 2 * d->hi : d->hi / 2; a.Wo = g.mode == 0 ? 2 * d->wi : d->wi / 2;
-    a.relu_in = d->relu_in; a.out_f32 = d->out_f32; a.relu_out = d->relu_out;
     if (g.mode == 0 && res) return XMC_EINVAL;
     if (g.mode == 1 && (mask || mask_bits)) return XMC_EINVAL;
-    const long long m = (long long)a.N * a.Ho * a.Wo;
-    const long long xb = (long long)a.N * a.Hi * a.Wi * a.Cin * 2;
-    const int ncb = (a.Cout + 31) / 32;
-    const long long wb = (long long)ncb * 32 * 16 * a.Cin * 2;
-    if (m >= (1ll << 31) || xb >= 0xfffffff0ll || wb >= 0xfffffff0ll) return XMC_EINVAL;
-    if (((uintptr_t)x % 16) || ((uintptr_t)w % 16) || ((uintptr_t)y % 16)) return XMC_EINVAL;
-    a.x_bytes = (unsigned)xb; a.w_bytes = (unsigned)wb;
-    a.nchunks = a.Cin / 32;
-    a.alpha = g.mode == 1 ? 0.25f * d->alpha : d->alpha; a.res_scale = d->res_scale; a.alpha_dev = d->alpha_dev;
-    a.log2_wt = ilog2_exact(g.wt); a.log2_rt = ilog2_exact(g.rt); a.log2_imgs = ilog2_exact(g.imgs);
-    a.log2_tx = ilog2_exact(g.wv) - a.log2_wt; a.log2_ty = ilog2_exact(g.hv) - a.log2_rt;
-    a.PW = g.wt + (g.waves4 ? 2 : 1); a.PR1 = g.rt + (g.waves4 ? 2 : 1); a.PP = g.pp;
-    a.pbuf_bytes = ((a.PP + 7) & ~7) * SPITCH_B;
-    a.magic_pw = 65536 / a.PW + 1; a.magic_pr1 = 65536 / a.PR1 + 1;
-    a.tiles_m = (int)g.tiles_m; a.tiles_n = g.tiles_n;
-    a.ksplit = ws ? g.ksplit : 1;
-    a.chunks_per_split = (a.nchunks + a.ksplit - 1) / a.ksplit;
-    a.ksplit = (a.nchunks + a.chunks_per_split - 1) / a.chunks_per_split;
-    a.ws = static_cast<float*>(ws);
-    if (a.ksplit > 1 && (y_bits || (mask_bits && !mask))) return XMC_EINVAL;     // the finishing kernel knows bf16 masks only
-    if ((mask_bits || y_bits) && (a.Cout % 16) != 0) return XMC_EINVAL;
-    a.mask_bits = a.ksplit > 1 ? nullptr : static_cast<const unsigned short*>(mask_bits);
-    a.y_bits = static_cast<unsigned short*>(y_bits);
+    if (!stream_args(&a, d, g.mode == 0 ? 2 * d->hi : d->hi / 2, g.mode == 0 ? 2 * d->wi : d->wi / 2, 16, d->cin, x, w, bias, mask, res, y))
+        return XMC_EINVAL;
+    a.mask_after = 0;
+    if (g.mode == 1) a.alpha = 0.25f * d->alpha;
+    xmc_plan_to_args(g.plan, &a);
+    a.tiles_n = g.tiles_n;
+    if (!xmc_settle_splitk(&a, g.ksplit, ws, mask, mask_bits, y_bits, true)) return XMC_EINVAL;
     hipStream_t s = static_cast<hipStream_t>(stream);
     if (xmc_internal_optin_conv_stream() != XMC_OK) return XMC_EINVAL;
     dim3 grid((unsigned)(a.tiles_m * a.tiles_n * a.ksplit * (g.mode == 0 && !g.waves4 ? 4 : 1)));
@@ -1468,53 +1453,39 @@ static int conv2d_phase(const xmc_conv_desc* d, const PhaseGeom& g, const void* 
         if (g.tile96) hipLaunchKernelGGL((conv_phase_kernel<1, 3, 2, 1>), grid, dim3(256), lds_bytes, s, a);
         else hipLaunchKernelGGL((conv_phase_kernel<1, 2, 4, 2>), grid, dim3(256), lds_bytes, s, a);
     }
-    if (a.ksplit > 1) {
-        const long long nvec = m * (a.Cout / 4);
-        hipLaunchKernelGGL(conv_splitk_finish_kernel, dim3((unsigned)((nvec + 255) / 256)), dim3(256), 0, s, a, nvec);
-    }
-    return xmc_hip_err(hipGetLastError());
+    return xmc_finish_splitk<conv_splitk_finish_kernel>(a, (long long)a.N * a.Ho * a.Wo, s);
 }
 
-// Launches the weight-streaming kernel on fragment-packed weights.  Returns XMC_OK, or XMC_EINVAL when the
-// shape is outside its domain (packed weights have no other consumer).
+// Tile plan of the 3x3 weight-streaming launch: 256-pixel tiles at most 64 wide on the output grid, one-pixel halo.
+static XmcTilePlan stream_plan(const xmc_conv_desc* d) {
+    const int up = d->ups ? 2 : 1;
+    return xmc_tile_plan(d->n, up * d->hi, up * d->wi, SBM, 64, 2, 4, NV_MAX * 256);
+}
+
 // Split-K factor of the weight-streaming kernel: layers with too few 256 x 128 tiles to occupy the chip (the 4x4 and
 // 8x8 layers: 84-336 workgroups walking 24-48 chunks each) split the 32-channel chunks over several workgroups.
-static int stream_ksplit(const xmc_conv_desc* d) {
+// tiles_m: stream_plan(d).tiles_m; the pointwise kernel counts 256-pixel tiles itself.
+static int stream_ksplit(const xmc_conv_desc* d, long long tiles_m) {
     if (d->dtype != XMC_BF16 || (d->cin % 32) != 0 || (d->ks != 3 && d->ks != 1) || !d->w_packed || (d->cout % 4) != 0 || d->pool_out)
         return 1;
-    const int ho = d->ups ? 2 * d->hi : d->hi, wo = d->ups ? 2 * d->wi : d->wi;
+    const int tiles_n = (d->cout + 127) / 128;
     if (d->ks == 1) {                                 // pointwise kernel: 256-pixel x 128-cout tiles, KC-channel stages
-        const int kc = (d->cin % 64) == 0 ? 64 : 32;
-        const long long tiles = (((long long)d->n * ho * wo + 255) / 256) * ((d->cout + 127) / 128);
-        const int nchunks = d->cin / kc;
+        const long long m = (long long)d->n * (d->ups ? 4 : 1) * d->hi * d->wi;
         // the partial sums cost 8 bytes of workspace traffic per output element and split: worth it only for very few tiles
-        const int target_pw = xmc_internal_tuning(XMC_TUNE_KSPLIT_TARGET_PW);
         // (round 4, full-step A/B at batch 56: no pointwise launch of the step gains from its split -- 0.15 ms per step without
         //  them, profiles/r04_ksplit_target_ab.txt; the split stays for launches with fewer than 48 tiles: batch-2-sized work)
-        if (tiles >= 48 || nchunks < 8) return 1;
-        int ks = (int)((target_pw + tiles / 2) / tiles);
-        if (ks > nchunks / 4) ks = nchunks / 4;
-        return ks < 2 ? 1 : ks;
+        return xmc_ksplit_for(((m + 255) / 256) * tiles_n, d->cin / ((d->cin % 64) == 0 ? 64 : 32), 48, 8,
+                              xmc_internal_tuning(XMC_TUNE_KSPLIT_TARGET_PW), 4);
     }
-    const int wt = wo < 64 ? wo : 64;
-    int rt = SBM / wt; if (rt > ho) rt = ho;
-    const int imgs = SBM / (wt * rt);
-    const long long tiles_m = (long long)((d->n + imgs - 1) / imgs) * (wo / wt) * (ho / rt);
-    const long long tiles = tiles_m * ((d->cout + 127) / 128);
-    const int nchunks = d->cin / 32;
     // (>= 16 chunks: at 8 chunks -- the ResNet-50's 256-channel 16^2 layers -- two splits of 4 chunks plus the float32
     //  round trip cost 63 us against 39 us unsplit)
-    if (tiles >= 384 || nchunks < 16) return 1;
     // target = workgroups the split aims at.  One per CU: a full-step A/B over 1 / 128 / 192 / 256 / 320 / 384 / 640 on one box
     // (profiles/r04_ksplit_target_ab.txt) has 256 ahead of 640 (round 3's value: 2.5 per CU) by 0.5 ms per step -- each split
     // beyond the first full wave of workgroups adds a float32 partial slab to write and re-read and hides nothing.
-    const int target = xmc_internal_tuning(XMC_TUNE_KSPLIT_TARGET);
-    int ks = (int)((target + tiles / 2) / tiles);
-    if (ks > nchunks / 4) ks = nchunks / 4;
-    return ks < 2 ? 1 : ks;
+    return xmc_ksplit_for(tiles_m * tiles_n, d->cin / 32, 384, 16, xmc_internal_tuning(XMC_TUNE_KSPLIT_TARGET), 4);
 }
 
-// 1 when this descriptor (w_packed bit 4 set) is inside the phase kernels' domain, else 0: the host-side mirror of phase_geom
+// 1 when this descriptor (XMC_CONV_PHASE set) is inside the phase kernels' domain, else 0: the host-side mirror of phase_geom
 extern "C" int xmc_conv2d_phase_supported(const xmc_conv_desc* d) {
     PhaseGeom g;
     return d && phase_geom(d, &g) ? 1 : 0;
@@ -1523,59 +1494,48 @@ extern "C" int xmc_conv2d_phase_supported(const xmc_conv_desc* d) {
 extern "C" int64_t xmc_conv2d_workspace_bytes(const xmc_conv_desc* d) {
     if (!d) return 0;
     PhaseGeom g;
-    if (phase_geom(d, &g))
-        return g.ksplit <= 1 ? 0 : (int64_t)g.ksplit * ((long long)d->n * (g.mode == 0 ? 4 : 1) * d->hi * d->wi / (g.mode == 0 ? 1 : 4)) * d->cout * 4;
-    if ((d->w_packed >> 4) & 1) return 0;
-    const int ks = stream_ksplit(d);
+    const bool phase = phase_geom(d, &g);
+    if (!phase && (d->w_packed & XMC_CONV_PHASE)) return 0;
+    // (the plan's fit is the launch's business: a 2 x 2 map, which the 3x3 launch rejects, is still answered here)
+    const int ks = phase ? g.ksplit : stream_ksplit(d, d->ks == 3 ? stream_plan(d).tiles_m : 0);
     if (ks <= 1) return 0;
-    const long long m = (long long)d->n * (d->ups ? 4 : 1) * d->hi * d->wi;
+    const long long m = phase && g.mode == 1 ? (long long)d->n * d->hi * d->wi / 4 : (long long)d->n * (d->ups ? 4 : 1) * d->hi * d->wi;
     return (int64_t)ks * m * d->cout * 4;
 }
 
+// Launches the weight-streaming kernels on fragment-packed weights.  Returns XMC_OK, or XMC_EINVAL when the
+// shape is outside their domain (packed weights have no other consumer).
 extern "C" int xmc_conv2d_stream(const xmc_conv_desc* d, const void* x, const void* w, const float* bias,
                                  const void* mask, const void* res, void* y, void* ws, const void* mask_bits, void* y_bits,
                                  void* stream) {
     if (d->dtype != XMC_BF16 || (d->cin % 32) != 0 || (d->ks != 3 && d->ks != 1)) return XMC_EINVAL;
-    if ((d->w_packed >> 4) & 1) {                    // 16-tap phase weights: no other kernel can read them
+    if (d->w_packed & XMC_CONV_PHASE) {              // 16-tap phase weights: no other kernel can read them
         PhaseGeom g;
         if (!phase_geom(d, &g)) return XMC_EINVAL;
         return conv2d_phase(d, g, x, w, bias, mask, res, y, ws, mask_bits, y_bits, stream);
     }
     SArgs a{};
-    a.x = x; a.w = w; a.bias = bias; a.mask = mask; a.res = res; a.y = y;
-    a.N = d->n; a.Hi = d->hi; a.Wi = d->wi; a.Cin = d->cin; a.Cout = d->cout;
-    a.Ho = d->ups ? 2 * d->hi : d->hi;
-    a.Wo = d->ups ? 2 * d->wi : d->wi;
-    a.ups = d->ups; a.relu_in = d->relu_in; a.res_ups = d->res_ups; a.out_f32 = d->out_f32; a.pool_out = d->pool_out;
-    a.relu_out = d->relu_out; a.mask_after = d->mask_after_res; a.valid_h = d->valid_h; a.valid_w = d->valid_w;
+    const int up = d->ups ? 2 : 1;
     XMC_REQUIRE(!(d->pool_out && (d->relu_out || d->mask_after_res || d->valid_h)));
-    if (d->pool_out && (a.Wo < 32 || mask || d->res_ups)) return XMC_EINVAL;   // pooled epilogue: 2x2 windows inside a wave
-    const int l2w = ilog2_exact(a.Wo), l2h = ilog2_exact(a.Ho);
-    if (l2w < 0 || l2h < 0) return XMC_EINVAL;
+    if (d->pool_out && (up * d->wi < 32 || mask || d->res_ups)) return XMC_EINVAL;   // pooled epilogue: 2x2 windows inside a wave
+    if (ilog2_exact(up * d->wi) < 0 || ilog2_exact(up * d->hi) < 0) return XMC_EINVAL;
+    if (!stream_args(&a, d, up * d->hi, up * d->wi, d->ks * d->ks, d->cin, x, w, bias, mask, res, y)) return XMC_EINVAL;
+    a.ups = d->ups; a.res_ups = d->res_ups; a.pool_out = d->pool_out; a.valid_h = d->valid_h; a.valid_w = d->valid_w;
     const long long m = (long long)a.N * a.Ho * a.Wo;
-    const long long xb = (long long)a.N * a.Hi * a.Wi * a.Cin * 2;
-    const int ncb = (a.Cout + 31) / 32;
-    const long long wb = (long long)ncb * 32 * d->ks * d->ks * a.Cin * 2;
-    if (m >= (1ll << 31) || xb >= 0xfffffff0ll || wb >= 0xfffffff0ll) return XMC_EINVAL;
-    if (((uintptr_t)x % 16) || ((uintptr_t)w % 16) || ((uintptr_t)y % 16)) return XMC_EINVAL;
-    a.x_bytes = (unsigned)xb; a.w_bytes = (unsigned)wb;
-    a.nchunks = a.Cin / 32;
-    a.alpha = d->alpha; a.res_scale = d->res_scale; a.alpha_dev = d->alpha_dev;
     hipStream_t s = static_cast<hipStream_t>(stream);
+    const bool compact = (d->w_packed & XMC_CONV_COMPACT) && d->valid_h > 0 && d->valid_h == d->valid_w && !d->ups;
     if (d->ks == 1) {
         if (d->pool_out) return XMC_EINVAL;
         const int kc = (a.Cin % 64) == 0 ? 64 : 32;
         a.nchunks = a.Cin / kc;
         a.tiles_n = (a.Cout + 127) / 128;
-        a.ksplit = ws ? stream_ksplit(d) : 1;
+        const int ksplit = ws ? stream_ksplit(d, 0) : 1;
         long long m_walk = m;                        // pixels the tiles walk (compact mode: the valid corners only)
-        // bit 6 of w_packed: compact -- walk only the valid_h x valid_h corner of every canvas; the margins of y are left
+        // XMC_CONV_COMPACT: walk only the valid_h x valid_h corner of every canvas; the margins of y are left
         // untouched (the caller keeps them zero).  Not with split-K (its finishing kernel walks the whole canvas and zeroes
         // the margins itself) and not with an upsampling gather.
-        a.vh = 0; a.magic_vv = a.magic_vh = 0;
-        if (((d->w_packed >> 6) & 1) && d->valid_h > 0 && d->valid_h == d->valid_w && d->valid_h < a.Ho && !d->ups && !d->res_ups && a.ksplit == 1) {
+        if (compact && d->valid_h < a.Ho && !d->res_ups && ksplit == 1) {
             a.vh = d->valid_h;
-            a.magic_vv = 0;
             a.magic_vh = (unsigned)(0x100000000ull / (unsigned)a.vh) + 1u;
             const long long mv = (long long)a.N * a.vh * a.vh;
             if (mv * a.vh >= 0x100000000ll) return XMC_EINVAL;
@@ -1587,32 +1547,26 @@ extern "C" int xmc_conv2d_stream(const xmc_conv_desc* d, const void* x, const vo
         // LDS / barrier / DMA latency of its stage loop is exposed (tools/pw_abl.sh: the MFMAs of a 1024 -> 256 layer on 22k
         // pixels are 6.8 us of a 35 us launch); measured on every 1x1 shape of the frozen ResNet-50 (tools/bench_resnet.py
         // --detail --pw-variant 4 / 8): 128 wins by 3-30 % up to 175k pixels and on the <= 64-cout layers at 351k, 256 by
-        // 2-8 % on the others.  w_packed bits 14-15: 1 forces 256, 2 forces 128.
-        const int tm_force = (d->w_packed >> 14) & 3;
+        // 2-8 % on the others.  XMC_CONV_PW_TILE_*: 1 forces 256, 2 forces 128.
+        const int tm_force = (d->w_packed >> XMC_CONV_PW_TILE_SHIFT) & XMC_CONV_PW_TILE_MASK;
         // Round 4: a LONG reduction with enough 256-pixel tiles to give every CU one takes the 256-pixel tile whatever the pixel
         // count -- the generator's fused conditional-BatchNorm projection (14,336 pixels, 1024 -> 4,224) and its data gradient
         // (4,224 -> 1024) re-read their weights half as often: 197 -> 182 us and 221 -> 152 us (tools/bench_pw.py --pw-variant 0 / 4);
         // the 384 -> 768 and shorter layers lose 20 % that way and keep 128.
-        const bool long_k = d->cin >= 1024 && a.ksplit == 1 && ((m_walk + 255) / 256) * (long long)a.tiles_n >= 256;
+        const bool long_k = d->cin >= 1024 && ksplit == 1 && ((m_walk + 255) / 256) * (long long)a.tiles_n >= 256;
         const int TMv = tm_force == 1 ? 256 : tm_force == 2 ? 128
                         : ((m_walk <= 200000 && !long_k) || (a.Cout <= 64 && m_walk <= 500000)) ? 128 : 256;
         a.tiles_m = (int)((m_walk + TMv - 1) / TMv);
-        a.chunks_per_split = (a.nchunks + a.ksplit - 1) / a.ksplit;
-        a.ksplit = (a.nchunks + a.chunks_per_split - 1) / a.chunks_per_split;
-        a.ws = static_cast<float*>(ws);
-        if (a.ksplit > 1 && (y_bits || (mask_bits && !mask))) return XMC_EINVAL;
-        if ((mask_bits || y_bits) && (a.Cout % 16) != 0) return XMC_EINVAL;
-        a.mask_bits = a.ksplit > 1 ? nullptr : static_cast<const unsigned short*>(mask_bits);
-        a.y_bits = static_cast<unsigned short*>(y_bits);
+        if (!xmc_settle_splitk(&a, ksplit, ws, mask, mask_bits, y_bits, true)) return XMC_EINVAL;
         if (xmc_internal_optin_conv_stream() != XMC_OK) return XMC_EINVAL;
         // persistent workgroups walk the tiles (two per CU: 72 KiB of LDS each); split-K launches stay one per (tile, split)
         long long nwg = (long long)a.tiles_m * a.tiles_n * a.ksplit;
         const int per_cu = TMv == 128 ? 3 : 2;
         if (a.ksplit == 1 && nwg > per_cu * xmc_cu_count()) nwg = per_cu * xmc_cu_count();
         dim3 grid((unsigned)nwg);
-        // bits 12-13 of w_packed: A/B hook of tools/bench_resnet.py (1 <32,3>, 2 <64,3>, 3 <32,4>); 0 = the shipped choice.
+        // XMC_CONV_PW_VARIANT_*: A/B hook of tools/bench_resnet.py (1 <32,3>, 2 <64,3>, 3 <32,4>); 0 = the shipped choice.
         // Measured: 32-channel stages x 3 (two workgroups per CU) wins on every ResNet-50 shape.  (No process-wide state.)
-        const int variant = ((d->w_packed >> 12) & 3) ? ((d->w_packed >> 12) & 3) : 1;
+        const int variant = (d->w_packed >> XMC_CONV_PW_VARIANT_SHIFT) & XMC_CONV_PW_VARIANT_MASK;
         if (variant == 2 && kc == 64 && TMv == 256) hipLaunchKernelGGL((conv_pw_kernel<64, 3>), grid, dim3(256), 3 * (256 * 128 + 16384), s, a);
         else {
             if (kc == 64) { a.nchunks *= 2; a.chunks_per_split *= 2; }       // 32-channel stages
@@ -1620,114 +1574,78 @@ extern "C" int xmc_conv2d_stream(const xmc_conv_desc* d, const void* x, const vo
             else if (variant == 3) hipLaunchKernelGGL((conv_pw_kernel<32, 4>), grid, dim3(256), 4 * (256 * 64 + 8192), s, a);
             else hipLaunchKernelGGL((conv_pw_kernel<32, 3>), grid, dim3(256), 3 * (256 * 64 + 8192), s, a);
         }
-        if (a.ksplit > 1) {
-            const long long nvec = m * (a.Cout / 4);
-            hipLaunchKernelGGL(conv_splitk_finish_kernel, dim3((unsigned)((nvec + 255) / 256)), dim3(256), 0, s, a, nvec);
-        }
-        return xmc_hip_err(hipGetLastError());
+        return xmc_finish_splitk<conv_splitk_finish_kernel>(a, m, s);
     }
-    const int halo = d->ks / 2;
-    a.vh = 0;
-    if (d->ks == 3 && ((d->w_packed >> 6) & 1) && d->valid_h > 0 && d->valid_h == d->valid_w && !d->ups && !d->pool_out) {
-        a.vh = d->valid_h;                           // compact: margin tiles are skipped, margin pixels of the other tiles are whatever
-        a.valid_h = a.valid_w = 0;                   // the convolution gives there (not zeroed) -- the caller reads the valid corner only
-    }
+    const XmcTilePlan plan = stream_plan(d);
+    if (!plan.fits) return XMC_EINVAL;
+    xmc_plan_to_args(plan, &a);
+    const int ksplit = ws ? stream_ksplit(d, plan.tiles_m) : 1;
+    if (compact && !d->pool_out) {
+        a.vh = ksplit == 1 ? d->valid_h : 0;         // compact: margin tiles are skipped (not under split-K, whose finishing kernel walks
+        a.valid_h = a.valid_w = 0;                   // every pixel: no uninitialised partial slabs), margin pixels of the other tiles are
+    }                                                // whatever the convolution gives there (not zeroed) -- the caller reads the valid corner only
     // 96-cout tiles (waves 4 x 1, 3 x 2 blocks each) where a 128-wide tile would leave a quarter of its MFMA slots and half
-    // of one wave pair's work empty: Cout = 96, 192 (the pooled epilogue needs the 128-pixel waves of the general shape)
-    const bool tile96 = d->ks == 3 && (a.Cout % 96) == 0 && (((a.Cout % 128) != 0 && a.Cout <= 192) || ((d->w_packed >> 9) & 1)) && !((d->w_packed >> 8) & 1);
-    // ... on 128-pixel tiles (three workgroups per CU) for the unsplit many-tile launches; w_packed bit 11: off (A/B)
+    // of one wave pair's work empty: Cout = 96, 192 (the pooled epilogue needs the 128-pixel waves of the general shape);
+    // XMC_CONV_FORCE_TILE96 / XMC_CONV_NO_TILE96: A/B
     // (round 4, measured and removed: 128-pixel x 96-cout tiles on four waves -- three workgroups per CU, 25-35 % slower -- and
     //  on three waves of 1 cout block x 4 pixel blocks -- half the weight bytes per MFMA, 8-10 % slower: DESIGN 11)
-    const int TPX = SBM;
-    const int wt = a.Wo < 64 ? a.Wo : 64;
-    int rt = TPX / wt; if (rt > a.Ho) rt = a.Ho;
-    const int imgs = TPX / (wt * rt);
-    a.log2_wt = ilog2_exact(wt); a.log2_rt = ilog2_exact(rt); a.log2_imgs = ilog2_exact(imgs);
-    a.log2_tx = l2w - a.log2_wt; a.log2_ty = l2h - a.log2_rt;
-    a.PW = wt + 2 * halo; a.PR1 = rt + 2 * halo;
-    a.PP = imgs * a.PR1 * a.PW;
-    if (a.PP * 4 > NV_MAX * 256) return XMC_EINVAL;
-    a.pbuf_bytes = ((a.PP + 7) & ~7) * SPITCH_B;
-    a.magic_pw = 65536 / a.PW + 1; a.magic_pr1 = 65536 / a.PR1 + 1;
-    a.tiles_m = ((a.N + imgs - 1) / imgs) << (a.log2_tx + a.log2_ty);
+    const bool tile96 = (a.Cout % 96) == 0 && (((a.Cout % 128) != 0 && a.Cout <= 192) || (d->w_packed & XMC_CONV_FORCE_TILE96)) &&
+                        !(d->w_packed & XMC_CONV_NO_TILE96);
     a.tiles_n = tile96 ? a.Cout / 96 : (a.Cout + 127) / 128;
-    const size_t lds_bytes = 2 * (size_t)a.pbuf_bytes;
-    a.ksplit = ws ? stream_ksplit(d) : 1;
-    if (a.ksplit > 1) a.vh = 0;                      // (the finishing kernel walks every pixel: no uninitialised partial slabs)
     // 64-cout tiles (waves 2 x 2 as in the general shape, ONE cout block per wave) for unsplit launches with at most one
     // 128-wide tile per CU: a lone workgroup has one wave per SIMD and every latency of its chunk loop is exposed (the frozen
     // ResNet-50's 256-channel 16^2 layers: 224 workgroups, 43 us for 15 us of MFMAs); twice the workgroups at half the
-    // accumulators each put two on a CU.  w_packed bit 10: off (A/B).
+    // accumulators each put two on a CU.  XMC_CONV_NO_TILE64: off (A/B).
     const int tile64_pct = xmc_internal_tuning(XMC_TUNE_TILE64_PCT);
-    const bool tile64 = d->ks == 3 && !tile96 && a.ksplit == 1 && (a.Cout % 64) == 0 && !((d->w_packed >> 10) & 1) &&
+    const bool tile64 = !tile96 && ksplit == 1 && (a.Cout % 64) == 0 && !(d->w_packed & XMC_CONV_NO_TILE64) &&
                         (long long)a.tiles_m * a.tiles_n * 100 <= (long long)xmc_cu_count() * tile64_pct;
     if (tile64) a.tiles_n = a.Cout / 64;
     // 32-cout tiles (four waves, ALL on pixels: 2 pixel blocks x 1 cout block each) for the <= 32-channel outputs -- the generator's
     // to-RGB convolution and the discriminator's image gradient (96 -> 3 at 128^2, three launches per step): in the 128-wide tile
-    // two of the four waves have no cout block at all and only stage.  w_packed bit 11: off (A/B).
-    const bool tile32 = d->ks == 3 && !tile96 && !tile64 && a.ksplit == 1 && a.Cout <= 32 && !((d->w_packed >> 11) & 1);
+    // two of the four waves have no cout block at all and only stage.  XMC_CONV_NO_TILE32: off (A/B).
+    const bool tile32 = !tile96 && !tile64 && ksplit == 1 && a.Cout <= 32 && !(d->w_packed & XMC_CONV_NO_TILE32);
     if (tile32) a.tiles_n = 1;
-    a.chunks_per_split = (a.nchunks + a.ksplit - 1) / a.ksplit;
-    a.ksplit = (a.nchunks + a.chunks_per_split - 1) / a.chunks_per_split;
-    a.ws = static_cast<float*>(ws);
-    if (a.ksplit > 1 && (y_bits || (mask_bits && !mask))) return XMC_EINVAL;
-    if ((mask_bits || y_bits) && (a.Cout % 16) != 0) return XMC_EINVAL;
-    a.mask_bits = a.ksplit > 1 ? nullptr : static_cast<const unsigned short*>(mask_bits);
-    a.y_bits = static_cast<unsigned short*>(y_bits);
+    if (!xmc_settle_splitk(&a, ksplit, ws, mask, mask_bits, y_bits, true)) return XMC_EINVAL;
     dim3 grid(a.tiles_m * a.tiles_n * a.ksplit);
+    const size_t lds_bytes = 2 * (size_t)a.pbuf_bytes;
     if (xmc_internal_optin_conv_stream() != XMC_OK) return XMC_EINVAL;
-    if (d->ks == 3 && tile96) hipLaunchKernelGGL((conv_stream_kernel<3, 3, 2, 1>), grid, dim3(256), lds_bytes, s, a);
-    else if (d->ks == 3 && tile64) hipLaunchKernelGGL((conv_stream_kernel<3, 1, 4, 2>), grid, dim3(256), lds_bytes, s, a);
-    else if (d->ks == 3 && tile32) hipLaunchKernelGGL((conv_stream_kernel<3, 1, 2, 1>), grid, dim3(256), lds_bytes, s, a);
-    else if (d->ks == 3) hipLaunchKernelGGL((conv_stream_kernel<3, 2, 4, 2>), grid, dim3(256), lds_bytes, s, a);
-    if (a.ksplit > 1) {
-        const long long nvec = m * (a.Cout / 4);
-        hipLaunchKernelGGL(conv_splitk_finish_kernel, dim3((unsigned)((nvec + 255) / 256)), dim3(256), 0, s, a, nvec);
-    }
-    return xmc_hip_err(hipGetLastError());
+    if (tile96) hipLaunchKernelGGL((conv_stream_kernel<3, 3, 2, 1>), grid, dim3(256), lds_bytes, s, a);
+    else if (tile64) hipLaunchKernelGGL((conv_stream_kernel<3, 1, 4, 2>), grid, dim3(256), lds_bytes, s, a);
+    else if (tile32) hipLaunchKernelGGL((conv_stream_kernel<3, 1, 2, 1>), grid, dim3(256), lds_bytes, s, a);
+    else hipLaunchKernelGGL((conv_stream_kernel<3, 2, 4, 2>), grid, dim3(256), lds_bytes, s, a);
+    return xmc_finish_splitk<conv_splitk_finish_kernel>(a, m, s);
 }
 
 
 // y = epilogue([x | x2'] W^T): the pointwise kernel over TWO sources (DUAL instantiations of conv_pw_kernel).  d describes the launch
-// as for xmc_conv2d_nhwc (ks = 1, bf16, fragment-packed w with K = d->cin + cin2, COMPACT: w_packed bit 6 and valid_h == valid_w = v,
-// 0 < v < ho); x2 is (n, h2, w2, cin2) and tile pixel (n, y, x) reads x2[n, stride2 * y, stride2 * x, :].  No split-K, no mask.
+// as for xmc_conv2d_nhwc (ks = 1, bf16, fragment-packed w with K = d->cin + cin2, COMPACT: XMC_CONV_COMPACT and valid_h == valid_w = v,
+// 0 < v < ho); x2 is (n, h2, w2, cin2) and tile pixel (n, y, x) reads x2[n, stride2 * y, stride2 * x, :].  No split-K.
 extern "C" int xmc_conv2d_pw_dual(const xmc_conv_desc* d, const void* x, const void* x2, int32_t cin2, int32_t h2, int32_t w2,
                                   int32_t stride2, const void* w, const float* bias, const void* mask, const void* res, void* y,
                                   const void* mask_bits, void* y_bits, void* stream) {
     XMC_REQUIRE(d && x && x2 && w && y);
-    XMC_REQUIRE(d->dtype == XMC_BF16 && d->ks == 1 && (d->w_packed & 1) && ((d->w_packed >> 6) & 1));
+    XMC_REQUIRE(d->dtype == XMC_BF16 && d->ks == 1 && (d->w_packed & XMC_CONV_PACKED) && (d->w_packed & XMC_CONV_COMPACT));
     XMC_REQUIRE((d->cin % 32) == 0 && cin2 > 0 && (cin2 % 32) == 0 && (d->cout % 4) == 0 && (stride2 == 1 || stride2 == 2 || stride2 == -2));
     XMC_REQUIRE(!d->ups && !d->res_ups && !d->pool_out && !d->out_f32 && !d->relu_in);
     XMC_REQUIRE(d->valid_h > 0 && d->valid_h == d->valid_w && d->valid_h < d->hi && d->hi == d->wi);
     if (stride2 > 0) XMC_REQUIRE(h2 >= stride2 * (d->valid_h - 1) + 1 && w2 >= stride2 * (d->valid_w - 1) + 1);
     else XMC_REQUIRE(h2 >= (d->valid_h + 1) / 2 && w2 >= (d->valid_w + 1) / 2);
-    XMC_REQUIRE((!y_bits && !mask_bits) || (d->cout % 16) == 0);
     SArgs a{};
-    a.x = x; a.w = w; a.bias = bias; a.res = res; a.y = y;
-    a.mask = mask; a.mask_bits = static_cast<const unsigned short*>(mask_bits); a.mask_after = d->mask_after_res;
-    a.N = d->n; a.Hi = a.Ho = d->hi; a.Wi = a.Wo = d->wi; a.Cin = d->cin; a.Cout = d->cout;
-    a.relu_out = d->relu_out;
-    a.x2 = x2; a.Cin2 = cin2; a.H2 = h2; a.W2 = w2; a.s2 = stride2;
-    if (ilog2_exact(a.Wo) < 0 || ilog2_exact(a.Ho) < 0) return XMC_EINVAL;
-    const long long xb = (long long)a.N * a.Hi * a.Wi * a.Cin * 2, x2b = (long long)a.N * h2 * w2 * cin2 * 2;
-    const int ncb = (a.Cout + 31) / 32;
-    const long long wb = (long long)ncb * 32 * (a.Cin + cin2) * 2;
-    if (xb >= 0xfffffff0ll || x2b >= 0xfffffff0ll || wb >= 0xfffffff0ll) return XMC_EINVAL;
-    if (((uintptr_t)x % 16) || ((uintptr_t)x2 % 16) || ((uintptr_t)w % 16) || ((uintptr_t)y % 16)) return XMC_EINVAL;
-    a.x_bytes = (unsigned)xb; a.x2_bytes = (unsigned)x2b; a.w_bytes = (unsigned)wb;
+    if (ilog2_exact(d->wi) < 0 || ilog2_exact(d->hi) < 0) return XMC_EINVAL;
+    const long long x2b = (long long)d->n * h2 * w2 * cin2 * 2;
+    if (!stream_args(&a, d, d->hi, d->wi, 1, d->cin + cin2, x, w, bias, mask, res, y) || !xmc_extents_ok(0, {x2b}, {x2})) return XMC_EINVAL;
+    a.x2 = x2; a.Cin2 = cin2; a.H2 = h2; a.W2 = w2; a.s2 = stride2; a.x2_bytes = (unsigned)x2b;
     a.nch1 = a.Cin / 32;
     a.nchunks = (a.Cin + cin2) / 32;                 // 32-channel stages
-    a.alpha = d->alpha; a.res_scale = d->res_scale; a.alpha_dev = d->alpha_dev;
     a.tiles_n = (a.Cout + 127) / 128;
-    a.ksplit = 1; a.chunks_per_split = a.nchunks;
+    if (!xmc_settle_splitk(&a, 1, nullptr, mask, mask_bits, y_bits, true)) return XMC_EINVAL;
     a.vh = d->valid_h;
     a.magic_vh = (unsigned)(0x100000000ull / (unsigned)a.vh) + 1u;
     const long long mv = (long long)a.N * a.vh * a.vh;
     if (mv * a.vh >= 0x100000000ll) return XMC_EINVAL;
-    const int tm_force = (d->w_packed >> 14) & 3;
+    const int tm_force = (d->w_packed >> XMC_CONV_PW_TILE_SHIFT) & XMC_CONV_PW_TILE_MASK;
     const int TMv = tm_force == 1 ? 256 : tm_force == 2 ? 128 : (mv <= 200000 || (a.Cout <= 64 && mv <= 500000)) ? 128 : 256;
     a.tiles_m = (int)((mv + TMv - 1) / TMv);
-    a.y_bits = static_cast<unsigned short*>(y_bits);
     if (xmc_internal_optin_conv_stream() != XMC_OK) return XMC_EINVAL;
     long long nwg = (long long)a.tiles_m * a.tiles_n;
     const int per_cu = TMv == 128 ? 3 : 2;

@@ -27,6 +27,7 @@
 #include <type_traits>
 
 #include "common.h"
+#include "conv_plan.h"
 
 #ifndef MX8_ABL
 #define MX8_ABL 0        // timing ablations (tools only; results are wrong): 1 no B-fragment reads, 2 no weight refills, 4 no patch staging
@@ -1014,77 +1015,39 @@ __global__ __launch_bounds__(256) void mx8_splitk_finish_kernel(const S8Args p, 
     else *reinterpret_cast<uint2*>(static_cast<bf16_t*>(p.y) + off) = make_uint2(pack_bf2(r[0], r[1]), pack_bf2(r[2], r[3]));
 }
 
-int mx8_ksplit(const xmc_conv_desc* d) {
+// Tile plan of the MX-fp8 launches: 256-pixel tiles at most 64 wide on an (n, h, w) grid; the patch (the tile plus `margin` rows and
+// columns) is staged as 5 vectors per pixel packet
+XmcTilePlan mx8_plan(int n, int h, int w, int margin) { return xmc_tile_plan(n, h, w, SBM, 64, margin, 5, NV_MAX * 256); }
+XmcTilePlan mx8_stream_plan(const xmc_conv_desc* d) {         // the 3x3 form: the output grid, one-pixel halo
+    const int up = d->ups ? 2 : 1;
+    return mx8_plan(d->n, up * d->hi, up * d->wi, 2);
+}
+
+int mx8_ksplit(const xmc_conv_desc* d, long long tiles_m) {
     if (d->pool_out) return 1;
-    const int ho = d->ups ? 2 * d->hi : d->hi, wo = d->ups ? 2 * d->wi : d->wi;
-    const int wt = wo < 64 ? wo : 64;
-    int rt = SBM / wt; if (rt > ho) rt = ho;
-    const int imgs = SBM / (wt * rt);
-    const long long tiles = (long long)((d->n + imgs - 1) / imgs) * (wo / wt) * (ho / rt) * ((d->cout + 127) / 128);
-    const int nchunks = (d->cin + 63) / 64;
-    if (tiles >= 384 || nchunks < 8) return 1;       // as the bf16 kernel: few-tile, long-K layers (4^2 / 8^2) only
-    int ks = (int)((640 + tiles / 2) / tiles);
-    if (ks > nchunks / 2) ks = nchunks / 2;
-    return ks < 2 ? 1 : ks;
+    // as the bf16 kernel: few-tile, long-K layers (4^2 / 8^2) only
+    return xmc_ksplit_for(tiles_m * ((d->cout + 127) / 128), (d->cin + 63) / 64, 384, 8, 640, 2);
 }
 
-// Geometry of the MX-fp8 "out" phase launch (w_packed bit 4 on the MX entry points): tiles of 256 LOW-resolution pixels, the
-// phase as a grid dimension.  The single source of truth of conv_phase_mx8_kernel's domain (xmc_conv2d_mx8_phase_supported).
-struct Mx8PhaseGeom { int wt, rt, imgs, pp, tiles_m, tiles_n, ksplit; };
-bool mx8_phase_geom(const xmc_conv_desc* d, Mx8PhaseGeom* g) {
-    if (!(d->w_packed & 1) || !((d->w_packed >> 4) & 1) || d->dtype != XMC_BF16 || d->ks != 3) return false;
-    if (!d->ups || d->pool_out) return false;        // the "in" form (pool_out) is not built
-    if (d->relu_in || d->res_ups || d->mask_after_res || d->valid_h || d->valid_w) return false;
+// Geometry of the MX-fp8 phase launches (XMC_CONV_PHASE on the MX entry points): tiles of 256 LOW-resolution pixels.  form 0, "out"
+// (xmc_conv2d_mx8 with ups): the grid is the input map, the phase a grid dimension; form 1, "in" (xmc_conv2d_mx8_phase_in*): the grid
+// is the pooled output map, the input parity in the K loop.  The single source of truth of the domains of conv_phase_mx8_kernel and
+// conv_phase_in_mx8_kernel (xmc_conv2d_mx8_phase_supported / xmc_conv2d_mx8_phase_in_supported).
+struct Mx8PhaseGeom { XmcTilePlan plan; int tiles_n, ksplit; };
+bool mx8_phase_geom(const xmc_conv_desc* d, int form, Mx8PhaseGeom* g) {
+    if (!(d->w_packed & XMC_CONV_PACKED) || !(d->w_packed & XMC_CONV_PHASE) || d->dtype != XMC_BF16 || d->ks != 3) return false;
+    if ((form == 0) != (d->ups != 0) || (form == 1) != (d->pool_out != 0)) return false;      // "out": ups only; "in": pool_out only
+    if (d->relu_in || (form == 1 && d->relu_out) || d->res_ups || d->mask_after_res || d->valid_h || d->valid_w) return false;
     if (d->n <= 0 || d->cin <= 0 || (d->cin % 64) != 0 || d->cout <= 0 || (d->cout % 32) != 0) return false;   // whole packets; the phase copies have rows % 32 == 0
-    if (d->hi < 2 || d->wi < 2 || ilog2_exact(d->hi) < 0 || ilog2_exact(d->wi) < 0) return false;
-    g->wt = d->wi < 64 ? d->wi : 64;
-    g->rt = SBM / g->wt; if (g->rt > d->hi) g->rt = d->hi;
-    g->imgs = SBM / (g->wt * g->rt);
-    g->pp = g->imgs * (g->rt + 1) * (g->wt + 1);
-    if (g->pp * 5 > NV_MAX * 256) return false;      // (2 x 2 maps: 64 images x 9 patch pixels)
-    const long long tiles_m = (long long)((d->n + g->imgs - 1) / g->imgs) * (d->wi / g->wt) * (d->hi / g->rt);
+    const int hv = form ? d->hi / 2 : d->hi, wv = form ? d->wi / 2 : d->wi, least = form ? 4 : 2;     // "in": output grids from 4 x 4
+    if (ilog2_exact(d->hi) < 0 || ilog2_exact(d->wi) < 0 || hv < least || wv < least) return false;
+    g->plan = mx8_plan(d->n, hv, wv, 1);
+    if (!g->plan.fits) return false;                 // ("out" on 2 x 2 maps: 64 images x 9 patch pixels)
     g->tiles_n = (d->cout + 127) / 128;
-    const long long wgs = tiles_m * g->tiles_n * 4;
+    const long long wgs = g->plan.tiles_m * g->tiles_n * (form ? 1 : 4);
     if (wgs >= (1ll << 24)) return false;
-    g->tiles_m = (int)tiles_m;
-    const int nchunks = d->cin / 64;
-    int ks = 1;
-    if (wgs < 384 && nchunks >= 8) {                 // as the bf16 phase kernels: few-tile, long-K layers (4^2 / 8^2) only
-        ks = (int)((xmc_internal_tuning(XMC_TUNE_KSPLIT_TARGET_PHASE) + wgs / 2) / wgs);
-        if (ks > nchunks / 2) ks = nchunks / 2;
-        if (ks < 2) ks = 1;
-    }
-    g->ksplit = ks;
-    return true;
-}
-
-// Geometry of the MX-fp8 "in" phase launch (xmc_conv2d_mx8_phase_in*): tiles of 256 OUTPUT (low-resolution) pixels, the input
-// parity in the K loop.  The single source of truth of conv_phase_in_mx8_kernel's domain (xmc_conv2d_mx8_phase_in_supported).
-bool mx8_phase_in_geom(const xmc_conv_desc* d, Mx8PhaseGeom* g) {
-    if (!(d->w_packed & 1) || !((d->w_packed >> 4) & 1) || d->dtype != XMC_BF16 || d->ks != 3) return false;
-    if (d->ups || !d->pool_out) return false;        // the "out" form is xmc_conv2d_mx8 with ups
-    if (d->relu_in || d->relu_out || d->res_ups || d->mask_after_res || d->valid_h || d->valid_w) return false;
-    if (d->n <= 0 || d->cin <= 0 || (d->cin % 64) != 0 || d->cout <= 0 || (d->cout % 32) != 0) return false;   // whole packets; the phase copies have rows % 32 == 0
-    if (d->hi < 8 || d->wi < 8 || ilog2_exact(d->hi) < 0 || ilog2_exact(d->wi) < 0) return false;             // output grids from 4 x 4
-    const int ho = d->hi / 2, wo = d->wi / 2;
-    g->wt = wo < 64 ? wo : 64;
-    g->rt = SBM / g->wt; if (g->rt > ho) g->rt = ho;
-    g->imgs = SBM / (g->wt * g->rt);
-    g->pp = g->imgs * (g->rt + 1) * (g->wt + 1);
-    if (g->pp * 5 > NV_MAX * 256) return false;
-    const long long tiles_m = (long long)((d->n + g->imgs - 1) / g->imgs) * (wo / g->wt) * (ho / g->rt);
-    g->tiles_n = (d->cout + 127) / 128;
-    const long long wgs = tiles_m * g->tiles_n;
-    if (wgs >= (1ll << 24)) return false;
-    g->tiles_m = (int)tiles_m;
-    const int nchunks = d->cin / 64;
-    int ks = 1;
-    if (wgs < 384 && nchunks >= 8) {                 // as the bf16 phase kernels: few-tile, long-K layers (4^2 / 8^2) only
-        ks = (int)((xmc_internal_tuning(XMC_TUNE_KSPLIT_TARGET_PHASE) + wgs / 2) / wgs);
-        if (ks > nchunks / 2) ks = nchunks / 2;
-        if (ks < 2) ks = 1;
-    }
-    g->ksplit = ks;
+    // as the bf16 phase kernels: few-tile, long-K layers (4^2 / 8^2) only
+    g->ksplit = xmc_ksplit_for(wgs, d->cin / 64, 384, 8, xmc_internal_tuning(XMC_TUNE_KSPLIT_TARGET_PHASE), 2);
     return true;
 }
 
@@ -1132,8 +1095,12 @@ extern "C" int xmc_mx8_probe(const void* a8, const void* as, const void* b8, con
 extern "C" int64_t xmc_conv2d_mx8_workspace_bytes(const xmc_conv_desc* d) {
     if (!d || d->ks != 3) return 0;
     Mx8PhaseGeom g;
-    if ((d->w_packed >> 4) & 1) { if (!mx8_phase_geom(d, &g)) return 0; }
-    const int ks = ((d->w_packed >> 4) & 1) ? g.ksplit : mx8_ksplit(d);
+    const bool phase = (d->w_packed & XMC_CONV_PHASE) != 0;
+    if (phase && !mx8_phase_geom(d, 0, &g)) return 0;
+    // Known wart, kept because the ABI's answers are: the 3x3 form is answered without asking whether the plan FITS, so a 4 x 4 map
+    // (56 x 4 x 4, 1536 -> 1536: 66,060,288 bytes) gets a workspace although xmc_conv2d_mx8_bits rejects it (16 images per tile, 576
+    // patch pixels); callers keep such maps on the bf16 kernel (ops._mx8_patch_fits).
+    const int ks = phase ? g.ksplit : mx8_ksplit(d, mx8_stream_plan(d).tiles_m);
     if (ks <= 1) return 0;
     const long long m = (long long)d->n * (d->ups ? 4 : 1) * d->hi * d->wi;
     return (int64_t)ks * m * d->cout * 4;
@@ -1141,114 +1108,70 @@ extern "C" int64_t xmc_conv2d_mx8_workspace_bytes(const xmc_conv_desc* d) {
 
 extern "C" int xmc_conv2d_mx8_phase_supported(const xmc_conv_desc* d) {
     Mx8PhaseGeom g;
-    return d && mx8_phase_geom(d, &g) ? 1 : 0;
+    return d && mx8_phase_geom(d, 0, &g) ? 1 : 0;
 }
 
-// the "out" phase form (d->w_packed bits 0 and 4, d->ups): w8 / wscale are the MX copy of the 16-tap phase weights
-static int conv2d_mx8_phase(const xmc_conv_desc* d, const void* x8, const void* w8, const void* wscale, const float* bias,
-                            const void* mask, const void* res, void* y, void* y8, int32_t y8_relu, void* ws,
-                            const void* mask_bits, void* y_bits, void* stream) {
-    Mx8PhaseGeom g;
-    if (!mx8_phase_geom(d, &g) || res) return XMC_EINVAL;
-    if ((mask_bits || y_bits) && (d->cout % 16) != 0) return XMC_EINVAL;
-    S8Args a;
-    a.x = x8; a.w = w8; a.wsc = wscale; a.bias = bias; a.mask = mask; a.res = nullptr; a.y = y;
-    a.y8 = y8; a.y8_relu = y8_relu; a.mx_rnd = xmc_mx_rnd();
-    a.relu_out = d->relu_out;
-    a.mask_bits = static_cast<const unsigned short*>(mask_bits); a.y_bits = static_cast<unsigned short*>(y_bits);
-    a.N = d->n; a.Hi = d->hi; a.Wi = d->wi; a.Cp = d->cin; a.Cout = d->cout;
-    a.Ho = 2 * d->hi; a.Wo = 2 * d->wi;
-    a.ups = 1; a.res_ups = 0; a.out_f32 = d->out_f32; a.pool_out = 0;
-    const long long m = (long long)a.N * a.Ho * a.Wo;
-    const long long xb = (long long)a.N * a.Hi * a.Wi * (a.Cp / 64) * 80;
-    const int ncb = (a.Cout + 31) / 32;
-    a.nchunks = a.Cp / 64;
-    const long long wb = (long long)ncb * a.nchunks * 16 * 2048, wsb = (long long)ncb * a.nchunks * 4 * 256;
-    if (m >= (1ll << 31) || xb >= 0xfffffff0ll || wb >= 0xfffffff0ll) return XMC_EINVAL;
-    if (((uintptr_t)x8 % 16) || ((uintptr_t)w8 % 16) || ((uintptr_t)y % 16) || ((uintptr_t)wscale % 4)) return XMC_EINVAL;
-    a.x_bytes = (unsigned)xb; a.w_bytes = (unsigned)wb; a.wsc_bytes = (unsigned)wsb;
-    a.alpha = d->alpha; a.res_scale = 0.f; a.alpha_dev = d->alpha_dev;
-    a.log2_wt = ilog2_exact(g.wt); a.log2_rt = ilog2_exact(g.rt); a.log2_imgs = ilog2_exact(g.imgs);
-    a.log2_tx = ilog2_exact(a.Wi) - a.log2_wt; a.log2_ty = ilog2_exact(a.Hi) - a.log2_rt;
-    a.PW = g.wt + 1; a.PR1 = g.rt + 1; a.PP = g.pp;
-    a.pbuf_bytes = ((a.PP + 7) & ~7) * SPITCH_B;
-    a.magic_pw = 65536 / a.PW + 1; a.magic_pr1 = 65536 / a.PR1 + 1;
-    a.tiles_m = g.tiles_m; a.tiles_n = g.tiles_n;
-    a.ksplit = ws ? g.ksplit : 1;
-    a.chunks_per_split = (a.nchunks + a.ksplit - 1) / a.ksplit;
-    a.ksplit = (a.nchunks + a.chunks_per_split - 1) / a.chunks_per_split;
-    a.ws = static_cast<float*>(ws);
-    if ((mask_bits || y_bits) && a.ksplit > 1) return XMC_EINVAL;       // the finishing pass neither reads nor writes bit masks
-    if (y8 && (a.ksplit > 1 || d->out_f32 || (a.Cout % 64) != 0 || ((uintptr_t)y8 % 16))) return XMC_EINVAL;
-    if (optin_mx8() != XMC_OK) return XMC_EINVAL;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    hipLaunchKernelGGL(conv_phase_mx8_kernel, dim3((unsigned)(a.tiles_m * a.tiles_n * a.ksplit * 4)), dim3(256),
-                       2 * (size_t)PBUF_BYTES + NV_MAX * 1024, s, a);
-    if (a.ksplit > 1) {
-        const long long nvec = m * (a.Cout / 4);
-        hipLaunchKernelGGL(mx8_splitk_finish_kernel, dim3((unsigned)((nvec + 255) / 256)), dim3(256), 0, s, a, nvec);
-    }
-    return xmc_hip_err(hipGetLastError());
-}
-
-// ---- the "in" phase form: avg_pool2(conv3x3(x)) on conv_phase_in_mx8_kernel.  d: hi / wi = the INPUT (high-resolution) map,
-// pool_out = 1, ups = 0, w_packed = 1 | 16; w8 / wscale = the MX copy (taps = 16) of the "in"-order 16-tap phase weights; res
-// and y at the output resolution.  Entry points of their own: on xmc_conv2d_mx8 the same descriptor stays XMC_EINVAL.
 extern "C" int xmc_conv2d_mx8_phase_in_supported(const xmc_conv_desc* d) {
     Mx8PhaseGeom g;
-    return d && mx8_phase_in_geom(d, &g) ? 1 : 0;
+    return d && mx8_phase_geom(d, 1, &g) ? 1 : 0;
 }
 
 extern "C" int64_t xmc_conv2d_mx8_phase_in_workspace_bytes(const xmc_conv_desc* d) {
     Mx8PhaseGeom g;
-    if (!d || !mx8_phase_in_geom(d, &g) || g.ksplit <= 1) return 0;
+    if (!d || !mx8_phase_geom(d, 1, &g) || g.ksplit <= 1) return 0;
     return (int64_t)g.ksplit * ((long long)d->n * (d->hi / 2) * (d->wi / 2)) * d->cout * 4;
+}
+
+// What every launcher of this file puts into S8Args first: operands, shapes (y is (n, ho, wo, cout)), scales and the byte extents of
+// the packets and of the MX weight copy (`taps` filter taps).  false: an operand is too large or misaligned.
+static bool mx8_args(S8Args* a, const xmc_conv_desc* d, int ho, int wo, int taps, const void* x8, const void* w8, const void* wscale,
+                     const float* bias, const void* mask, const void* res, void* y, void* y8, int32_t y8_relu) {
+    a->x = x8; a->w = w8; a->wsc = wscale; a->bias = bias; a->mask = mask; a->res = res; a->y = y;
+    a->y8 = y8; a->y8_relu = y8_relu; a->mx_rnd = xmc_mx_rnd();
+    a->relu_out = d->relu_out;
+    a->N = d->n; a->Hi = d->hi; a->Wi = d->wi; a->Cp = (d->cin + 63) & ~63; a->Cout = d->cout; a->Ho = ho; a->Wo = wo;
+    a->ups = d->ups; a->res_ups = d->res_ups; a->out_f32 = d->out_f32; a->pool_out = d->pool_out;
+    a->alpha = d->alpha; a->res_scale = d->res_scale; a->alpha_dev = d->alpha_dev;
+    a->nchunks = a->Cp / 64;
+    const long long pin = (long long)a->N * a->Hi * a->Wi, pout = (long long)a->N * ho * wo, ncb = (a->Cout + 31) / 32;
+    const long long xb = pin * a->nchunks * 80, wb = ncb * a->nchunks * taps * 2048, wsb = ncb * a->nchunks * ((taps + 3) / 4) * 256;
+    if (!xmc_extents_ok(pin > pout ? pin : pout, {xb, wb}, {x8, w8, y}) || ((uintptr_t)wscale % 4)) return false;
+    a->x_bytes = (unsigned)xb; a->w_bytes = (unsigned)wb; a->wsc_bytes = (unsigned)wsb;
+    return true;
+}
+
+// The phase forms (XMC_CONV_PACKED | XMC_CONV_PHASE; w8 / wscale are the MX copy, taps = 16, of the 16-tap phase weights).
+// form 0, "out": conv3x3(upsample2(x)) on conv_phase_mx8_kernel (d->ups; no res).  form 1, "in": avg_pool2(conv3x3(x)) on
+// conv_phase_in_mx8_kernel (d: hi / wi = the INPUT (high-resolution) map, pool_out = 1, ups = 0; the "in"-order copy; res and y at the
+// output resolution; no mask) -- entry points of its own: on xmc_conv2d_mx8 the same descriptor stays XMC_EINVAL.
+static int conv2d_mx8_phase(const xmc_conv_desc* d, int form, const void* x8, const void* w8, const void* wscale, const float* bias,
+                            const void* mask, const void* res, void* y, void* y8, int32_t y8_relu, void* ws,
+                            const void* mask_bits, void* y_bits, void* stream) {
+    Mx8PhaseGeom g;
+    if (!mx8_phase_geom(d, form, &g) || (form == 0 ? res != nullptr : (mask || mask_bits))) return XMC_EINVAL;
+    S8Args a{};
+    if (!mx8_args(&a, d, form ? d->hi / 2 : 2 * d->hi, form ? d->wi / 2 : 2 * d->wi, 16, x8, w8, wscale, bias, mask, res, y, y8, y8_relu))
+        return XMC_EINVAL;
+    a.ups = form ? 0 : 1; a.pool_out = 0;            // ("in": the finishing pass sees a plain launch on Ho x Wo)
+    if (form) a.alpha = 0.25f * d->alpha;            // the 1/4 of the average pooling
+    else a.res_scale = 0.f;
+    xmc_plan_to_args(g.plan, &a);
+    a.tiles_n = g.tiles_n;
+    if (!xmc_settle_splitk(&a, g.ksplit, ws, mask, mask_bits, y_bits, false, y8)) return XMC_EINVAL;
+    if (optin_mx8() != XMC_OK) return XMC_EINVAL;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const dim3 grid((unsigned)(a.tiles_m * a.tiles_n * a.ksplit * (form ? 1 : 4)));
+    const size_t lds_bytes = 2 * (size_t)PBUF_BYTES + NV_MAX * 1024;           // two patch buffers + the parked patch offsets
+    if (form) hipLaunchKernelGGL(conv_phase_in_mx8_kernel, grid, dim3(256), lds_bytes, s, a);
+    else hipLaunchKernelGGL(conv_phase_mx8_kernel, grid, dim3(256), lds_bytes, s, a);
+    return xmc_finish_splitk<mx8_splitk_finish_kernel>(a, (long long)a.N * a.Ho * a.Wo, s);
 }
 
 extern "C" int xmc_conv2d_mx8_phase_in_bits(const xmc_conv_desc* d, const void* x8, const void* w8, const void* wscale,
                                             const float* bias, const void* res, void* y, void* y8, int32_t y8_relu,
                                             void* ws, void* y_bits, void* stream) {
     XMC_REQUIRE(d && x8 && w8 && wscale && y);
-    Mx8PhaseGeom g;
-    if (!mx8_phase_in_geom(d, &g)) return XMC_EINVAL;
-    if (y_bits && (d->cout % 16) != 0) return XMC_EINVAL;
-    S8Args a;
-    a.x = x8; a.w = w8; a.wsc = wscale; a.bias = bias; a.mask = nullptr; a.res = res; a.y = y;
-    a.y8 = y8; a.y8_relu = y8_relu; a.mx_rnd = xmc_mx_rnd();
-    a.relu_out = 0; a.mask_bits = nullptr; a.y_bits = static_cast<unsigned short*>(y_bits);
-    a.N = d->n; a.Hi = d->hi; a.Wi = d->wi; a.Cp = d->cin; a.Cout = d->cout;
-    a.Ho = d->hi / 2; a.Wo = d->wi / 2;
-    a.ups = 0; a.res_ups = 0; a.out_f32 = d->out_f32; a.pool_out = 0;      // (the finishing pass sees a plain launch on Ho x Wo)
-    const long long m = (long long)a.N * a.Ho * a.Wo;
-    const long long xb = 4 * m * (a.Cp / 64) * 80;
-    const int ncb = (a.Cout + 31) / 32;
-    a.nchunks = a.Cp / 64;
-    const long long wb = (long long)ncb * a.nchunks * 16 * 2048, wsb = (long long)ncb * a.nchunks * 4 * 256;
-    if (4 * m >= (1ll << 31) || xb >= 0xfffffff0ll || wb >= 0xfffffff0ll) return XMC_EINVAL;
-    if (((uintptr_t)x8 % 16) || ((uintptr_t)w8 % 16) || ((uintptr_t)y % 16) || ((uintptr_t)wscale % 4)) return XMC_EINVAL;
-    a.x_bytes = (unsigned)xb; a.w_bytes = (unsigned)wb; a.wsc_bytes = (unsigned)wsb;
-    a.alpha = 0.25f * d->alpha; a.res_scale = d->res_scale; a.alpha_dev = d->alpha_dev;      // the 1/4 of the average pooling
-    a.log2_wt = ilog2_exact(g.wt); a.log2_rt = ilog2_exact(g.rt); a.log2_imgs = ilog2_exact(g.imgs);
-    a.log2_tx = ilog2_exact(a.Wo) - a.log2_wt; a.log2_ty = ilog2_exact(a.Ho) - a.log2_rt;
-    a.PW = g.wt + 1; a.PR1 = g.rt + 1; a.PP = g.pp;
-    a.pbuf_bytes = ((a.PP + 7) & ~7) * SPITCH_B;
-    a.magic_pw = 65536 / a.PW + 1; a.magic_pr1 = 65536 / a.PR1 + 1;
-    a.tiles_m = g.tiles_m; a.tiles_n = g.tiles_n;
-    a.ksplit = ws ? g.ksplit : 1;
-    a.chunks_per_split = (a.nchunks + a.ksplit - 1) / a.ksplit;
-    a.ksplit = (a.nchunks + a.chunks_per_split - 1) / a.chunks_per_split;
-    a.ws = static_cast<float*>(ws);
-    if (y_bits && a.ksplit > 1) return XMC_EINVAL;                       // the finishing pass writes no bit masks
-    if (y8 && (a.ksplit > 1 || d->out_f32 || (a.Cout % 64) != 0 || ((uintptr_t)y8 % 16))) return XMC_EINVAL;
-    if (optin_mx8() != XMC_OK) return XMC_EINVAL;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    hipLaunchKernelGGL(conv_phase_in_mx8_kernel, dim3((unsigned)(a.tiles_m * a.tiles_n * a.ksplit)), dim3(256),
-                       2 * (size_t)PBUF_BYTES + NV_MAX * 1024, s, a);
-    if (a.ksplit > 1) {
-        const long long nvec = m * (a.Cout / 4);
-        hipLaunchKernelGGL(mx8_splitk_finish_kernel, dim3((unsigned)((nvec + 255) / 256)), dim3(256), 0, s, a, nvec);
-    }
-    return xmc_hip_err(hipGetLastError());
+    return conv2d_mx8_phase(d, 1, x8, w8, wscale, bias, nullptr, res, y, y8, y8_relu, ws, nullptr, y_bits, stream);
 }
 
 extern "C" int xmc_conv2d_mx8_phase_in(const xmc_conv_desc* d, const void* x8, const void* w8, const void* wscale,
@@ -1262,68 +1185,30 @@ extern "C" int xmc_conv2d_mx8_phase_in(const xmc_conv_desc* d, const void* x8, c
 // xmc_conv2d_nhwc_bits (bits: launches without split-K, cout % 16 == 0).  Everything else as xmc_conv2d_nhwc_ws.
 extern "C" int xmc_conv2d_mx8_bits(const xmc_conv_desc* d, const void* x8, const void* w8, const void* wscale,
                                    const float* bias, const void* mask, const void* res, void* y, void* y8, int32_t y8_relu,
-                                   void* ws, const void* mask_bits, void* y_bits, void* stream);
+                                   void* ws, const void* mask_bits, void* y_bits, void* stream) {
+    XMC_REQUIRE(d && x8 && w8 && wscale && y);
+    if (d->w_packed & XMC_CONV_PHASE)                // 16-tap phase weights: the "out" form or nothing
+        return conv2d_mx8_phase(d, 0, x8, w8, wscale, bias, mask, res, y, y8, y8_relu, ws, mask_bits, y_bits, stream);
+    if (d->ks != 3 || d->relu_in || d->mask_after_res || d->valid_h || (d->cout % 4) != 0) return XMC_EINVAL;
+    if (d->pool_out && d->relu_out) return XMC_EINVAL;
+    const int up = d->ups ? 2 : 1;
+    if (d->pool_out && (up * d->wi < 32 || mask || mask_bits || d->res_ups)) return XMC_EINVAL;
+    if (ilog2_exact(up * d->wi) < 0 || ilog2_exact(up * d->hi) < 0) return XMC_EINVAL;
+    S8Args a{};
+    if (!mx8_args(&a, d, up * d->hi, up * d->wi, 9, x8, w8, wscale, bias, mask, res, y, y8, y8_relu)) return XMC_EINVAL;
+    const XmcTilePlan plan = mx8_stream_plan(d);
+    if (!plan.fits) return XMC_EINVAL;
+    xmc_plan_to_args(plan, &a);
+    a.tiles_n = (a.Cout + 127) / 128;
+    if (!xmc_settle_splitk(&a, mx8_ksplit(d, plan.tiles_m), ws, mask, mask_bits, y_bits, false, y8)) return XMC_EINVAL;
+    if (optin_mx8() != XMC_OK) return XMC_EINVAL;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    hipLaunchKernelGGL(conv_stream_mx8_kernel, dim3(a.tiles_m * a.tiles_n * a.ksplit), dim3(256), 2 * (size_t)PBUF_BYTES + NV_MAX * 1024, s, a);   // two patch buffers + the parked patch offsets
+    return xmc_finish_splitk<mx8_splitk_finish_kernel>(a, (long long)a.N * a.Ho * a.Wo, s);
+}
 
 extern "C" int xmc_conv2d_mx8(const xmc_conv_desc* d, const void* x8, const void* w8, const void* wscale,
                               const float* bias, const void* mask, const void* res, void* y, void* y8, int32_t y8_relu,
                               void* ws, void* stream) {
     return xmc_conv2d_mx8_bits(d, x8, w8, wscale, bias, mask, res, y, y8, y8_relu, ws, nullptr, nullptr, stream);
-}
-
-extern "C" int xmc_conv2d_mx8_bits(const xmc_conv_desc* d, const void* x8, const void* w8, const void* wscale,
-                                   const float* bias, const void* mask, const void* res, void* y, void* y8, int32_t y8_relu,
-                                   void* ws, const void* mask_bits, void* y_bits, void* stream) {
-    XMC_REQUIRE(d && x8 && w8 && wscale && y);
-    if ((d->w_packed >> 4) & 1)                      // 16-tap phase weights: the "out" form or nothing
-        return conv2d_mx8_phase(d, x8, w8, wscale, bias, mask, res, y, y8, y8_relu, ws, mask_bits, y_bits, stream);
-    if (d->ks != 3 || d->relu_in || d->mask_after_res || d->valid_h || (d->cout % 4) != 0) return XMC_EINVAL;
-    if (d->pool_out && d->relu_out) return XMC_EINVAL;
-    if ((mask_bits || y_bits) && (d->cout % 16) != 0) return XMC_EINVAL;
-    S8Args a;
-    a.x = x8; a.w = w8; a.wsc = wscale; a.bias = bias; a.mask = mask; a.res = res; a.y = y;
-    a.y8 = y8; a.y8_relu = y8_relu; a.mx_rnd = xmc_mx_rnd();
-    a.relu_out = d->relu_out;
-    a.mask_bits = static_cast<const unsigned short*>(mask_bits); a.y_bits = static_cast<unsigned short*>(y_bits);
-    a.N = d->n; a.Hi = d->hi; a.Wi = d->wi; a.Cp = (d->cin + 63) & ~63; a.Cout = d->cout;
-    a.Ho = d->ups ? 2 * d->hi : d->hi;
-    a.Wo = d->ups ? 2 * d->wi : d->wi;
-    a.ups = d->ups; a.res_ups = d->res_ups; a.out_f32 = d->out_f32; a.pool_out = d->pool_out;
-    if (d->pool_out && (a.Wo < 32 || mask || mask_bits || d->res_ups)) return XMC_EINVAL;
-    const int l2w = ilog2_exact(a.Wo), l2h = ilog2_exact(a.Ho);
-    if (l2w < 0 || l2h < 0) return XMC_EINVAL;
-    const long long m = (long long)a.N * a.Ho * a.Wo;
-    const long long xb = (long long)a.N * a.Hi * a.Wi * (a.Cp / 64) * 80;
-    const int ncb = (a.Cout + 31) / 32;
-    a.nchunks = a.Cp / 64;
-    const long long wb = (long long)ncb * a.nchunks * 9 * 2048, wsb = (long long)ncb * a.nchunks * 3 * 256;
-    if (m >= (1ll << 31) || xb >= 0xfffffff0ll || wb >= 0xfffffff0ll) return XMC_EINVAL;
-    if (((uintptr_t)x8 % 16) || ((uintptr_t)w8 % 16) || ((uintptr_t)y % 16) || ((uintptr_t)wscale % 4)) return XMC_EINVAL;
-    a.x_bytes = (unsigned)xb; a.w_bytes = (unsigned)wb; a.wsc_bytes = (unsigned)wsb;
-    a.alpha = d->alpha; a.res_scale = d->res_scale; a.alpha_dev = d->alpha_dev;
-    const int wt = a.Wo < 64 ? a.Wo : 64;
-    int rt = SBM / wt; if (rt > a.Ho) rt = a.Ho;
-    const int imgs = SBM / (wt * rt);
-    a.log2_wt = ilog2_exact(wt); a.log2_rt = ilog2_exact(rt); a.log2_imgs = ilog2_exact(imgs);
-    a.log2_tx = l2w - a.log2_wt; a.log2_ty = l2h - a.log2_rt;
-    a.PW = wt + 2; a.PR1 = rt + 2;
-    a.PP = imgs * a.PR1 * a.PW;
-    if (a.PP * 5 > NV_MAX * 256) return XMC_EINVAL;
-    a.pbuf_bytes = ((a.PP + 7) & ~7) * SPITCH_B;
-    a.magic_pw = 65536 / a.PW + 1; a.magic_pr1 = 65536 / a.PR1 + 1;
-    a.tiles_m = ((a.N + imgs - 1) / imgs) << (a.log2_tx + a.log2_ty);
-    a.tiles_n = (a.Cout + 127) / 128;
-    a.ksplit = ws ? mx8_ksplit(d) : 1;
-    a.chunks_per_split = (a.nchunks + a.ksplit - 1) / a.ksplit;
-    a.ksplit = (a.nchunks + a.chunks_per_split - 1) / a.chunks_per_split;
-    a.ws = static_cast<float*>(ws);
-    if ((mask_bits || y_bits) && a.ksplit > 1) return XMC_EINVAL;       // the finishing pass neither reads nor writes bit masks
-    if (y8 && (a.ksplit > 1 || d->out_f32 || (a.Cout % 64) != 0 || ((uintptr_t)y8 % 16))) return XMC_EINVAL;   // the twin is written by the kernel's own epilogue
-    if (optin_mx8() != XMC_OK) return XMC_EINVAL;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    hipLaunchKernelGGL(conv_stream_mx8_kernel, dim3(a.tiles_m * a.tiles_n * a.ksplit), dim3(256), 2 * (size_t)PBUF_BYTES + NV_MAX * 1024, s, a);   // two patch buffers + the parked patch offsets
-    if (a.ksplit > 1) {
-        const long long nvec = m * (a.Cout / 4);
-        hipLaunchKernelGGL(mx8_splitk_finish_kernel, dim3((unsigned)((nvec + 255) / 256)), dim3(256), 0, s, a, nvec);
-    }
-    return xmc_hip_err(hipGetLastError());
 }

@@ -366,10 +366,10 @@ static int wgrad_dispatch(const xmc_wgrad_desc* d, const void* x, const void* dy
     XMC_REQUIRE(d && (query || (x && dy && dw)));
     XMC_REQUIRE(d->ks == 1 || d->ks == 3);
     XMC_REQUIRE(d->dtype == XMC_F32 || d->dtype == XMC_BF16);
-    const int variant = d->variant & 15;   // (bits 4.. : tuning bits of the LDS-DMA kernel, A/B benchmarks only)
+    const int variant = d->variant & XMC_WGRAD_KERNEL_MASK;   // (the other fields: A/B hooks of the kernels below)
     if (variant != 0) {                    // variant: 0 generic kernel only, 1 auto, 2 skip the LDS-DMA kernel (A/B benchmarks)
         // next to a 2x resampling (x_ups / dy_ups): 16 (phase, tap) products per low-resolution pixel instead of 36
-        // (conv_wgrad_phase.hip; needs the workspace; bit 8 of variant: off)
+        // (conv_wgrad_phase.hip; needs the workspace; XMC_WGRAD_NO_PHASE: off)
         int rc = variant == 2 ? 1 : xmc_conv2d_wgrad_phase_try(d, x, dy, dw, db, ws, query, stream);
         if (rc != 1) return rc;
         rc = variant == 2 ? 1 : xmc_conv2d_wgrad_dma_try(d, x, dy, dw, db, ws, query, stream);   // LDS-DMA staged, 3-stage ring

@@ -604,14 +604,14 @@ extern "C" int xmc_conv2d_wgrad_dma_try(const xmc_wgrad_desc* d, const void* x, 
     a.PP = a.imgs * a.PR1 * a.PW;
     if (a.PP > 192) return 1;
     a.magic_pw = 65536 / a.PW + 1; a.magic_pr1 = 65536 / a.PR1 + 1;
-    // 1x1: cin blocks per workgroup (bits 9-10 of variant force 1 / 2 / 4 for A/B runs): 2 where the channel count allows
+    // 1x1: cin blocks per workgroup (XMC_WGRAD_FORCE_* forces 1 / 2 / 4 for A/B runs): 2 where the channel count allows
     int cb = 1;
     if (d->ks == 1 && a.PP <= 64) {
         // measured (tools/bench_wgrad_1x1.py): 2 blocks -10..-25 % from 2k pixels up, 4 blocks only on the widest launch
         // (4224 couts: 344 -> 230 us); below 2k pixels the single block's 2x workgroups win
         if (m >= 2048 && (a.Cin % 128) == 0 && a.Cout >= 2048) cb = 4;
         else if (m >= 2048 && (a.Cin % 64) == 0) cb = 2;
-        const int force = (d->variant >> 9) & 3;
+        const int force = (d->variant >> XMC_WGRAD_FORCE_SHIFT) & XMC_WGRAD_FORCE_MASK;
         if (force == 1) cb = 1;
         else if (force == 2 && (a.Cin % 64) == 0) cb = 2;
         else if (force == 3 && (a.Cin % 128) == 0) cb = 4;
@@ -620,8 +620,8 @@ extern "C" int xmc_conv2d_wgrad_dma_try(const xmc_wgrad_desc* d, const void* x, 
     a.stage_bytes = YS_BYTES + xi * 4 * 1024;
     // 96-cout tiles where they waste fewer zero couts than 128-cout ones (Cout = 96, 192, 288: every channel count of the
     // network is a multiple of 96); the one instantiation covers the 16-pixel-wide tiles (maps >= 16 x 16), where those
-    // layers live.  (bit 11 of variant: off -- A/B)
-    const bool c96 = d->ks == 3 && xi == 2 && a.PW == 18 && cb == 1 && !((d->variant >> 11) & 1) &&
+    // layers live.  (XMC_WGRAD_NO_C96: off -- A/B)
+    const bool c96 = d->ks == 3 && xi == 2 && a.PW == 18 && cb == 1 && !(d->variant & XMC_WGRAD_NO_C96) &&
                      ((a.Cout + 95) / 96) * 96 < ((a.Cout + 127) / 128) * 128;
     a.tiles_i = c96 ? (a.Cout + 95) / 96 : (a.Cout + 127) / 128;
     a.cchunks = a.Cin / (32 * cb);
@@ -633,8 +633,8 @@ extern "C" int xmc_conv2d_wgrad_dma_try(const xmc_wgrad_desc* d, const void* x, 
     // not by its re-reads.  Per layer the table does split: ~1536 workgroups are 5-11 % faster on the >= 64^2 maps (few
     // slabs, long pixel loops) and 8-15 % slower on the <= 32^2 ones, hence the rule below.  The XCD-aware order is kept for
     // its HBM traffic (the sharers of a dY tile / x patch hit one L2).
-    // (tune = variant >> 4 of tools/bench_conv.py overrides: bit 0 launch order, bits 1-3 workgroup target)
-    const int tune = (d->variant >> 4) & 15;
+    // (tune = the XMC_WGRAD_TUNE_* field, tools/bench_conv.py, overrides: bit 0 launch order, bits 1-3 workgroup target)
+    const int tune = (d->variant >> XMC_WGRAD_TUNE_SHIFT) & XMC_WGRAD_TUNE_MASK;
     static const int targets[8] = {0, 768, 512, 1536, 2048, 3072, 4096, 1024};
     const int max_split = (a.ntiles + 3) / 4;
     auto split_for = [&](int target_wg) {
@@ -663,8 +663,8 @@ extern "C" int xmc_conv2d_wgrad_dma_try(const xmc_wgrad_desc* d, const void* x, 
     a.overwrite = overwrite && nsplit == 1;
     dim3 grid(slabs * nsplit), block(256);
     hipStream_t s = static_cast<hipStream_t>(stream);
-    // 4 x 4 maps: two-stage ring, two workgroups per CU (see the kernel's NST; bit 13 of variant: three stages -- A/B)
-    const bool nst2 = d->ks == 3 && xi == 3 && a.PW == 6 && cb == 1 && !c96 && !((d->variant >> 13) & 1);
+    // 4 x 4 maps: two-stage ring, two workgroups per CU (see the kernel's NST; XMC_WGRAD_NST3: three stages -- A/B)
+    const bool nst2 = d->ks == 3 && xi == 3 && a.PW == 6 && cb == 1 && !c96 && !(d->variant & XMC_WGRAD_NST3);
     const size_t lds_bytes = (nst2 ? 2 : 3) * (size_t)a.stage_bytes;
     if (xmc_internal_optin_wgrad_dma() != XMC_OK) return 1;
     bool launched = false;

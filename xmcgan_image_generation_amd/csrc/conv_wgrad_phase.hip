@@ -340,7 +340,7 @@ extern "C" int xmc_conv2d_wgrad_phase_try(const xmc_wgrad_desc* d, const void* x
                                           float* ws, long long* query, void* stream) {
     if (d->dtype != XMC_BF16 || d->ks != 3 || (d->cin % 32) != 0 || (d->cout % 32) != 0) return 1;
     if ((d->x_ups != 0) == (d->dy_ups != 0)) return 1;
-    if ((d->variant >> 8) & 1) return 1;                  // A/B switch (XMC_PHASE_CONV=0)
+    if (d->variant & XMC_WGRAD_NO_PHASE) return 1;                  // A/B switch (XMC_PHASE_CONV=0)
     if (d->x_ups && d->x_relu) return 1;
     const int form = d->x_ups ? 0 : 1;
     WPArgs a{};
@@ -375,9 +375,10 @@ extern "C" int xmc_conv2d_wgrad_phase_try(const xmc_wgrad_desc* d, const void* x
     a.ntiles = (int)(m / DPT);
     const int slabs = a.tiles_i * a.cchunks;
     const int max_split = (a.ntiles + 3) / 4;
-    static const int targets[8] = {768, 768, 512, 1536, 2048, 3072, 4096, 1024};      // (bits 5-7 of variant: A/B sweep of tools/)
+    static const int targets[8] = {768, 768, 512, 1536, 2048, 3072, 4096, 1024};      // (XMC_WGRAD_PHASE_TARGET_*: A/B sweep of tools/)
     const int t_env = xmc_internal_tuning(XMC_TUNE_WGRAD_TARGET_PHASE);
-    int ns = ((((d->variant >> 5) & 7) == 0 && t_env ? t_env : targets[(d->variant >> 5) & 7]) + slabs - 1) / slabs;
+    const int ti = (d->variant >> XMC_WGRAD_PHASE_TARGET_SHIFT) & XMC_WGRAD_PHASE_TARGET_MASK;
+    int ns = ((ti == 0 && t_env ? t_env : targets[ti]) + slabs - 1) / slabs;
     if (ns > max_split) ns = max_split;
     if (ns < 1) ns = 1;
     const int tps = (a.ntiles + ns - 1) / ns;

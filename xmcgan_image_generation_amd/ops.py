@@ -31,6 +31,11 @@ def _code(dt):
     raise TypeError(f"unsupported dtype {dt}")
 
 
+def _env_on(name, default=True):
+    """an on / off switch from the environment: off only when the variable is "0" (unset: ``default``)"""
+    return os.environ.get(name, "1" if default else "0") != "0"
+
+
 def _p(t):
     if t is None:
         return None
@@ -58,6 +63,41 @@ class HipOps:
 
     name = "hip-gfx950"
 
+    # (attribute, environment variable, default): the on / off switches ``__init__`` reads -- off means the variable is "0"
+    _SWITCHES = (
+        # conv3x3 next to a 2x resampling as four 2x2 convolutions (conv_phase_kernel); XMC_PHASE_CONV=0: A/B switch
+        ("phase_conv", "XMC_PHASE_CONV", True),
+        ("phase4", "XMC_PHASE4", True),                # "out" form: phases as waves (0: as workgroups; A/B)
+        ("px128", "XMC_PHASE_PX128", True),            # ... on 128-pixel x 64-cout tiles where they fit (A/B)
+        ("attn_mfma", "XMC_ATTN_MFMA", True),          # attention_for_g on MFMA tiles in the bf16 mode (A/B)
+        ("wl_fused", "XMC_WL_FUSED", True),            # word_loss fused on the matrix cores in the bf16 mode (A/B)
+        ("mask_bits", "XMC_MASK_BITS", True),          # ReLU masks as bits in the conv epilogues (A/B)
+        ("compact_pw", "XMC_RESNET_COMPACT", True),    # ResNet-50 1x1 layers on the valid corner of their canvases
+        ("tile64", "XMC_TILE64", True),                # A/B: 64-cout tiles on unsplit few-tile 3x3 launches
+        ("tile32", "XMC_TILE32", True),                # A/B: 32-cout tiles for the <= 32-channel outputs (to-RGB)
+        ("no_split_k", "XMC_NO_SPLIT_K", False),       # A/B: forward / dgrad convolutions without split-K
+        # MX-fp8 mode: the resampling-adjacent layers stay on the bf16 phase kernels (2.25x fewer MFMAs; XMC_FP8_PHASE=0: the fp8
+        # 3x3 kernel there too, 2x the MFMA rate).  Round 3 measured the fp8 kernel ahead (C4 53.7 vs 54.5 ms); with round 4's phase
+        # kernels it is behind -- round 5, same box, alternated (profiles/r05_c4_vs_c3.txt): C3 bf16 45.2 ms, C4 with fp8 everywhere
+        # 46.8 / 47.0, C4 with the bf16 phase kernels 45.5 / 45.7 -> ON.  (Weight gradients are bf16 in either mode.)
+        ("fp8_phase", "XMC_FP8_PHASE", True),
+        # round 7: ... and their "out" form (ups launches: G's first block convolution, the data gradient of D's pooled convolution)
+        # on the MX-fp8 phase kernel (conv_phase_mx8_kernel: 16 block-scaled products per low-resolution pixel) -- both factors at
+        # once.  Needs fp8 and fp8_phase; the "in" form (pool_out launches) stays on the bf16 phase kernels unless fp8_phase_in_mx
+        # (below).  Off by default (config.conv_fp8_phase; XMC_FP8_PHASE_MX=1: A/B override for bench.py --config c4)
+        ("fp8_phase_mx", "XMC_FP8_PHASE_MX", False),
+        # round 8: ... and their "in" form (pool_out launches: the second convolution of D's down-sampling blocks, the data gradient
+        # of G's first block convolution) on conv_phase_in_mx8_kernel -- the input parity in the K loop, whole packets at pixel
+        # stride 2.  A switch of its own (either, both or neither): needs fp8 and fp8_phase.  Off by default
+        # (config.conv_fp8_phase_in; XMC_FP8_PHASE_IN_MX=1: A/B override for bench.py --config c4)
+        ("fp8_phase_in_mx", "XMC_FP8_PHASE_IN_MX", False),
+        # deterministic reductions: split-K weight gradients, bias gradients and pooled sums go through caller-owned
+        # workspaces and fixed-order second stages instead of float atomics (bit-reproducible gradients);
+        # XMC_DETERMINISTIC=0 restores the single-pass atomic variants (A/B benchmarks)
+        ("deterministic", "XMC_DETERMINISTIC", True),
+        ("keep_grads", "XMC_KEEP_GRADS", False),       # see fuse_opt (__init__)
+    )
+
     def __init__(self, dtype=torch.bfloat16, device=None, wgrad_variant=1, stream_conv=None, wgrad_async=None):
         if not torch.cuda.is_available():
             raise _lib.XmcError("HipOps needs a ROCm GPU (torch.cuda.is_available() is False); "
@@ -67,40 +107,19 @@ class HipOps:
         self.code = _code(dtype)
         self.device = torch.device(device if device is not None else f"cuda:{torch.cuda.current_device()}")
         # XMC_WGRAD_TUNE: A/B knob for the split-K target / launch order of conv_wgrad_dma.hip (tools/bench_conv.py --wgrad-tunes)
-        self.wgrad_variant = wgrad_variant | (int(os.environ.get("XMC_WGRAD_TUNE", "0")) << 4)
-        if os.environ.get("XMC_WGRAD_NST3", "0") != "0":                       # A/B: three-stage ring on the 4 x 4 maps too (variant bit 13)
-            self.wgrad_variant |= 0x2000
-        if os.environ.get("XMC_WGRAD_C96", "1") == "0":                        # A/B: no 96-cout tiles in conv_wgrad_dma (variant bit 11)
-            self.wgrad_variant |= 0x800
-        # conv3x3 next to a 2x resampling as four 2x2 convolutions (conv_phase_kernel); XMC_PHASE_CONV=0: A/B switch
-        self.phase_conv = os.environ.get("XMC_PHASE_CONV", "1") != "0"
-        self.phase4 = os.environ.get("XMC_PHASE4", "1") != "0"                 # "out" form: phases as waves (0: as workgroups; A/B)
-        self.attn_mfma = os.environ.get("XMC_ATTN_MFMA", "1") != "0"           # attention_for_g on MFMA tiles in the bf16 mode (A/B)
-        self.wl_fused = os.environ.get("XMC_WL_FUSED", "1") != "0"             # word_loss fused on the matrix cores in the bf16 mode (A/B)
-        self.px128 = os.environ.get("XMC_PHASE_PX128", "1") != "0"            # ... on 128-pixel x 64-cout tiles where they fit (A/B)
-        self.mask_bits = os.environ.get("XMC_MASK_BITS", "1") != "0"           # ReLU masks as bits in the conv epilogues (A/B)
-        self.compact_pw = os.environ.get("XMC_RESNET_COMPACT", "1") != "0"     # ResNet-50 1x1 layers on the valid corner of their canvases
-        self.tile64 = os.environ.get("XMC_TILE64", "1") != "0"                # A/B: 64-cout tiles on unsplit few-tile 3x3 launches
-        self.tile32 = os.environ.get("XMC_TILE32", "1") != "0"                # A/B: 32-cout tiles for the <= 32-channel outputs (to-RGB)
-        self.pw_variant = int(os.environ.get("XMC_PW_VARIANT", "0"))          # A/B: pointwise kernel variant bits (w_packed 12-15)
-        self.no_split_k = os.environ.get("XMC_NO_SPLIT_K", "0") != "0"        # A/B: forward / dgrad convolutions without split-K
-        # MX-fp8 mode: the resampling-adjacent layers stay on the bf16 phase kernels (2.25x fewer MFMAs; XMC_FP8_PHASE=0: the fp8
-        # 3x3 kernel there too, 2x the MFMA rate).  Round 3 measured the fp8 kernel ahead (C4 53.7 vs 54.5 ms); with round 4's phase
-        # kernels it is behind -- round 5, same box, alternated (profiles/r05_c4_vs_c3.txt): C3 bf16 45.2 ms, C4 with fp8 everywhere
-        # 46.8 / 47.0, C4 with the bf16 phase kernels 45.5 / 45.7 -> ON.  (Weight gradients are bf16 in either mode.)
-        self.fp8_phase = os.environ.get("XMC_FP8_PHASE", "1") != "0"
-        # round 7: ... and their "out" form (ups launches: G's first block convolution, the data gradient of D's pooled convolution)
-        # on the MX-fp8 phase kernel (conv_phase_mx8_kernel: 16 block-scaled products per low-resolution pixel) -- both factors at
-        # once.  Needs fp8 and fp8_phase; the "in" form (pool_out launches) stays on the bf16 phase kernels unless fp8_phase_in_mx (below).  Off by default
-        # (config.conv_fp8_phase; XMC_FP8_PHASE_MX=1: A/B override for bench.py --config c4)
-        self.fp8_phase_mx = os.environ.get("XMC_FP8_PHASE_MX", "0") != "0"
+        self.wgrad_variant = wgrad_variant | (int(os.environ.get("XMC_WGRAD_TUNE", "0")) << _lib.XMC_WGRAD_TUNE_SHIFT)
+        if _env_on("XMC_WGRAD_NST3", False):                                   # A/B: three-stage ring on the 4 x 4 maps too
+            self.wgrad_variant |= _lib.XMC_WGRAD_NST3
+        if not _env_on("XMC_WGRAD_C96"):                                       # A/B: no 96-cout tiles in conv_wgrad_dma
+            self.wgrad_variant |= _lib.XMC_WGRAD_NO_C96
+        for attr, env, default in self._SWITCHES:
+            setattr(self, attr, _env_on(env, default))
+        self.force_tile128 = self.force_tile96 = False                         # A/B pokes of tools/bench_conv.py --tile-ab (XMC_CONV_NO_TILE96 / _FORCE_TILE96)
+        self.pw_variant = int(os.environ.get("XMC_PW_VARIANT", "0"))          # A/B: pointwise kernel variant + pixel tile (XMC_CONV_PW_VARIANT_* / _PW_TILE_*)
+        self.last_conv_route = None           # the route ``conv`` took last (``_conv_route``)
+        self.last_conv_phase = False          # ... was it phase-decomposed?  (bench.py: such a launch executes 4/9 of the 3x3 formulation's MFMAs)
         self.last_conv_mx8_phase = False      # did the last ``conv`` run on conv_phase_mx8_kernel?  (tests: no silent fallback)
         self.mx8_phase_launches = 0           # ... and how many did since this table was made
-        # round 8: ... and their "in" form (pool_out launches: the second convolution of D's down-sampling blocks, the data gradient
-        # of G's first block convolution) on conv_phase_in_mx8_kernel -- the input parity in the K loop, whole packets at pixel
-        # stride 2.  A switch of its own (either, both or neither): needs fp8 and fp8_phase.  Off by default
-        # (config.conv_fp8_phase_in; XMC_FP8_PHASE_IN_MX=1: A/B override for bench.py --config c4)
-        self.fp8_phase_in_mx = os.environ.get("XMC_FP8_PHASE_IN_MX", "0") != "0"
         self.last_conv_mx8_phase_in = False   # did the last ``conv`` run on conv_phase_in_mx8_kernel?  (tests: no silent fallback)
         self.mx8_phase_in_launches = 0        # ... and how many did since this table was made
         # race hunt: 1 = every MX convolution quantises its input itself (producer packets ignored), 2 = the
@@ -123,17 +142,13 @@ class HipOps:
         check(self.lib.xmc_create(self._dev_index, C.byref(self._handle)), f"xmc_create(device {self._dev_index})")
         # 3x3 bf16 convolutions on the weight-streaming kernel (prepared weights in MFMA-fragment order);
         # XMC_CONV_STREAM=0 keeps every layer on the LDS-staged kernels (A/B benchmarks)
-        self.stream_conv = (os.environ.get("XMC_CONV_STREAM", "1") != "0") if stream_conv is None else stream_conv
+        self.stream_conv = _env_on("XMC_CONV_STREAM") if stream_conv is None else stream_conv
         # weight-gradient launches on their own HIP stream: nothing but the optimiser consumes them, so they run
         # beside the data-gradient chain and fill the CUs its small-grid / tail phases leave idle (join_wgrad)
         # (off by default: xmc_gan overlaps the two pullbacks of train_g_d instead and switches this on where it pays)
-        self.wgrad_async = (os.environ.get("XMC_WGRAD_ASYNC", "0") != "0") if wgrad_async is None else wgrad_async
+        self.wgrad_async = _env_on("XMC_WGRAD_ASYNC", False) if wgrad_async is None else wgrad_async
         self._wg_stream = None
         self._wg_keep = []
-        # deterministic reductions: split-K weight gradients, bias gradients and pooled sums go through caller-owned
-        # workspaces and fixed-order second stages instead of float atomics (bit-reproducible gradients);
-        # XMC_DETERMINISTIC=0 restores the single-pass atomic variants (A/B benchmarks)
-        self.deterministic = os.environ.get("XMC_DETERMINISTIC", "1") != "0"
         # BASELINE config #5 (config.conv_fp8): the 3x3 convolutions (forward + data gradient) multiply MX-fp8 operands
         # -- e4m3 elements, one e8m0 scale per 32 channels, block-scaled MFMA with float32 accumulation; weight
         # gradients, 1x1 / RGB layers, normalisation, attention and every loss stay as in the bf16 mode
@@ -141,33 +156,32 @@ class HipOps:
         # round 4: 1 / sigma of the spectrally-normalised layers rides in the convolution's alpha (xmc_conv_desc.alpha_dev), so
         # the prepared weights are a pure cast of W: one batched pass per forward writes every copy AND the first product of
         # the power iteration (xmc_wprep_batched); XMC_FOLD_SIGMA=0: the round-3 path (A/B, and the float32 parity mode)
-        self.fold_sigma = (os.environ.get("XMC_FOLD_SIGMA", "1") != "0") and dtype == torch.bfloat16
+        self.fold_sigma = _env_on("XMC_FOLD_SIGMA") and dtype == torch.bfloat16
         # ... and the gradient through sigma + the zeroing of the consumed gradient ride in the Adam kernel
-        # (xmc_adam_ema_dev_sn); keep_grads: write the FINAL gradient back instead of zeros (tests / tools that read the
+        # (xmc_adam_ema_dev_sn); keep_grads (XMC_KEEP_GRADS=1): write the FINAL gradient back instead of zeros (tests / tools that read the
         # gradient arenas after a step) -- the next half step then zero-fills as before
-        self.fuse_opt = (os.environ.get("XMC_FUSE_OPT", "1") != "0") and dtype == torch.bfloat16
-        self.keep_grads = os.environ.get("XMC_KEEP_GRADS", "0") != "0"
+        self.fuse_opt = _env_on("XMC_FUSE_OPT") and dtype == torch.bfloat16
         # round 5: every gradient tensor of a half step has exactly ONE producing launch, so that launch WRITES it
         # (XMC_WGRAD_OVERWRITE, gemm beta = 0) instead of adding into a zeroed arena: the optimiser kernel neither zeroes what it
         # consumed (4 B/param less) nor do the reducing passes read the old value (4 B/param less); ParamArena audits on the
         # first update that every leaf was written.  XMC_FIRST_WRITE=0: the round-4 path (A/B)
-        self.first_write = self.fuse_opt and self.deterministic and os.environ.get("XMC_FIRST_WRITE", "1") != "0"
+        self.first_write = self.fuse_opt and self.deterministic and _env_on("XMC_FIRST_WRITE")
         # round 5: the optimiser kernel emits the prepared weight copies of the batched-preparation tables while it holds the new
         # W (xmc_adam_wprep_tiles): no separate pass re-reads the masters Adam just wrote.  XMC_FUSE_PREP=0: A/B
         # Measured (profiles/r05_ab_fuse_prep.txt, same box): G/D-only 26.05 / 25.88 ms with the separate pass, 26.16 / 26.29 fused --
         # the separate pass runs on the side stream beside the generator's forward pass, the fused copies sit in the optimiser
         # kernels on the critical path.  OFF by default; bit-identical either way (tests/test_gpu_fused_opt.py).
-        self.fuse_prep = self.fuse_opt and self.fold_sigma and os.environ.get("XMC_FUSE_PREP", "0") != "0"
+        self.fuse_prep = self.fuse_opt and self.fold_sigma and _env_on("XMC_FUSE_PREP", False)
         # round 5: the gamma / beta maps of the LOCAL conditional-BatchNorm sites (one fused 1024 -> 4,224 projection at 16 x 16)
         # and their gradients in bf16 -- what the reference's nn.Conv(dtype=bfloat16) produces (layers.py:261-273) -- instead of
         # float32: 242 MB per map less to write and re-read in every pass, and no cast in front of the projection's backward
-        self.gb_bf16 = dtype == torch.bfloat16 and os.environ.get("XMC_GB_BF16", "1") != "0"
+        self.gb_bf16 = dtype == torch.bfloat16 and _env_on("XMC_GB_BF16")
 
     def resnet_step_mode(self):
         """may ResNet50Features.forward(reuse_buffers=True) take the training step's launches -- compact pointwise launches into
         persistent buffers, dual-source launches, the fused stem?  (bf16 weight-streaming path only: the float32 parity mode and the
         fp8 mode keep fresh tensors and the reference-shaped launches)"""
-        return bool(getattr(self, "compact_pw", False) and self.dtype == torch.bfloat16 and self.stream_conv and not self.fp8)
+        return bool(self.compact_pw and self.dtype == torch.bfloat16 and self.stream_conv and not self.fp8)
 
     def set_fp8_scale_rule(self, rule):
         """MX-fp8 scale rule of every quantiser (xmc_set_tuning("mx8_scale_floor"), process-wide like the other knobs): "next_binade"
@@ -252,6 +266,29 @@ class HipOps:
             return True
         return (2 if ups else 1) * x.shape[2] >= 32
 
+    def _conv_flags(self, phase=False, compact=False):
+        """xmc_conv_desc.w_packed of a launch on fragment-packed weights -- the only place that builds it.  The A/B hooks ride
+        on every descriptor: an entry point ignores the ones of kernels it does not launch."""
+        f = _lib.XMC_CONV_PACKED | ((self.pw_variant & 3) << _lib.XMC_CONV_PW_VARIANT_SHIFT) | (((self.pw_variant >> 2) & 3) << _lib.XMC_CONV_PW_TILE_SHIFT)
+        for on, bit in ((phase, _lib.XMC_CONV_PHASE), (phase and not self.phase4, _lib.XMC_CONV_PHASE_PER_WG),
+                        (phase and not self.px128, _lib.XMC_CONV_NO_PX128), (compact, _lib.XMC_CONV_COMPACT),
+                        (self.force_tile128, _lib.XMC_CONV_NO_TILE96), (self.force_tile96, _lib.XMC_CONV_FORCE_TILE96),
+                        (not self.tile64, _lib.XMC_CONV_NO_TILE64), (not self.tile32, _lib.XMC_CONV_NO_TILE32)):
+            if on:
+                f |= bit
+        return f
+
+    def _bit_masks(self, mask, y, cout, *, emit_bits, out_f32, split, read_mask=True):
+        """-> (mask_bits, y_bits) of a launch on fragment-packed weights: the ReLU mask read as bits (``mask.bits``) and the
+        tensor that receives (y > 0) as bits -- one uint16 per 16 channels; a split-K launch can do neither"""
+        if not self.mask_bits or cout % 16 or split:
+            return None, None
+        mbits = getattr(mask, "bits", None) if mask is not None and read_mask else None
+        ybits = None
+        if emit_bits and not out_f32:
+            ybits = torch.empty(tuple(y.shape[:-1]) + (cout // 16,), dtype=torch.int16, device=self.device)
+        return mbits, ybits
+
     def _conv_pw_dual(self, x, x2, w, bias, *, ks, res, relu_out, valid, emit_bits, compact, out, x2_stride, alpha, res_scale, mask=None,
                       mask_after_res=False):
         """y = epilogue([x | x2(s y, s x)] W^T) on conv_pw_kernel's DUAL instantiation: the down-sampling bottleneck's
@@ -263,14 +300,9 @@ class HipOps:
         assert tuple(out.shape) == (n, hi, wi, w.cout) and out.dtype == self.dtype and out.is_contiguous() and x2.is_contiguous()
         assert res is None or tuple(res.shape) == tuple(out.shape)
         assert mask is None or (tuple(mask.shape) == tuple(out.shape) and mask.dtype == self.dtype)
-        self.last_conv_phase = self.last_conv_mx8_phase = self.last_conv_mx8_phase_in = False
-        d = ConvDesc(n, hi, wi, cin, w.cout, 1, 0, 0, 0, 0, self.code, float(alpha), float(res_scale), 1 | 64 | ((getattr(self, "pw_variant", 0) & 15) << 12),
+        d = ConvDesc(n, hi, wi, cin, w.cout, 1, 0, 0, 0, 0, self.code, float(alpha), float(res_scale), self._conv_flags(compact=True),
                      0, int(relu_out), int(mask_after_res), int(valid), int(valid), None)
-        ybits = mbits = None
-        if self.mask_bits and w.cout % 16 == 0:
-            mbits = getattr(mask, "bits", None) if mask is not None else None
-            if emit_bits:
-                ybits = torch.empty((n, hi, wi, w.cout // 16), dtype=torch.int16, device=self.device)
+        mbits, ybits = self._bit_masks(mask, out, w.cout, emit_bits=emit_bits, out_f32=False, split=False)
         check(self.lib.xmc_conv2d_pw_dual(C.byref(d), _p(x), _p(x2), x2.shape[-1], x2.shape[1], x2.shape[2], int(x2_stride), _p(w.data), _p(bias),
                                           _p(mask), _p(res), _p(out), _p(mbits), _p(ybits), self._stream()), "xmc_conv2d_pw_dual")
         if ybits is not None:
@@ -285,8 +317,9 @@ class HipOps:
         fwd = w.phase[0] == "s2in"
         return self._phase_ok(w, w.phase[0], hi, wi, not fwd, fwd)
 
-    def _phase_flags(self):
-        return 1 | 16 | (32 if not self.phase4 else 0) | (128 if not getattr(self, "px128", True) else 0)
+    def _geometry_desc(self, hi, wi, cin, cout, ups, pool_out):
+        """a one-image 3x3 phase descriptor for the C side's ``*_supported`` queries"""
+        return ConvDesc(1, hi, wi, cin, cout, 3, int(bool(ups)), 0, 0, 0, self.code, 1.0, 1.0, self._conv_flags(phase=True), int(bool(pool_out)), 0, 0, 0, 0)
 
     def _phase_ok(self, w, kind, hi, wi, ups, pool_out):
         """may this launch run phase-decomposed (conv_phase_kernel)?  needs the 16-tap copy of the right kind and exactly
@@ -294,8 +327,43 @@ class HipOps:
         (xmc_conv2d_phase_supported: one source of truth for the tile / patch limits)."""
         if not self.phase_conv or (self.fp8 and not self.fp8_phase) or w.phase is None or w.phase[0] != kind or bool(ups) == bool(pool_out):
             return False
-        d = ConvDesc(1, hi, wi, w.cin, w.cout, 3, int(bool(ups)), 0, 0, 0, self.code, 1.0, 1.0, self._phase_flags(), int(bool(pool_out)), 0, 0, 0, 0)
-        return bool(self.lib.xmc_conv2d_phase_supported(C.byref(d)))
+        return bool(self.lib.xmc_conv2d_phase_supported(C.byref(self._geometry_desc(hi, wi, w.cin, w.cout, ups, pool_out))))
+
+    # routes of ``conv``: which kernel family a launch takes
+    ROUTES = ("plain", "stream3", "pointwise", "pw_dual", "phase_out", "phase_in", "phase_s2", "mx8", "mx8_phase_out", "mx8_phase_in")
+
+    def _conv_route(self, w, hi, wi, cin, *, ks, ups, pool_out, stride2=False, relu_out=False, has_res=False, res_ups=False,
+                    has_mask=False, mask_after_res=False, valid=0, dual=False):
+        """Which kernel family does this launch of ``conv`` take (one of ``ROUTES``)?  Launches nothing, allocates nothing.
+        (hi, wi, cin): the input; ups / pool_out: after ``stride2`` was resolved into one of them.  In order of precedence:
+        "pw_dual" (a second source), "plain" (unpacked weights: the LDS-staged kernels), the phase-decomposed kernels where the
+        weight carries the 16-tap copy of the right kind and the C side says the launch is in their domain -- "phase_s2" (the
+        stride-2 copies), "mx8_phase_out" / "mx8_phase_in" (MX-fp8 operands: the switch is on, the weight carries the MX twin of
+        its phase copy and the C side agrees), else "phase_out" / "phase_in" on bf16 -- then "mx8" (the MX-fp8 3x3 kernel where it
+        pays), else the weight-streaming "stream3" / "pointwise" kernels."""
+        if dual:
+            return "pw_dual"
+        if not isinstance(w, PackedWeight):
+            return "plain"
+        cout, bf16 = w.cout, self.dtype == torch.bfloat16
+        # conv3x3(upsample2(.)) / avg_pool2(conv3x3(.)) as four 2x2 convolutions on the low-resolution grid (2.25x fewer MFMAs)
+        if (ks == 3 and not (res_ups or mask_after_res or valid) and (stride2 or not relu_out)
+                and ((ups and not has_res and self._phase_ok(w, "s2out" if stride2 else "out", hi, wi, True, False))
+                     or (pool_out and not has_mask and self._phase_ok(w, "s2in" if stride2 else "in", hi, wi, False, True)))):
+            if stride2:
+                return "phase_s2"
+            mx = self.fp8 and not relu_out and bf16 and w.phase_mx8 is not None
+            if mx and ups and self.fp8_phase_mx and self._mx8_phase_ok(hi, wi, cin, cout):
+                return "mx8_phase_out"
+            if mx and pool_out and self.fp8_phase_in_mx and w.phase[0] == "in" and self._mx8_phase_in_ok(hi, wi, cin, cout):
+                return "mx8_phase_in"
+            return "phase_out" if ups else "phase_in"
+        # MX-fp8 where it pays: rows are padded to 64 channels, so a 96-channel input would do 128 channels of work and its
+        # (large, 128^2) tensor would pay the quantisation pass on top -- measured 0.74x the bf16 kernel; those stay bf16
+        if (self.fp8 and ks == 3 and bf16 and not (mask_after_res or valid) and not (relu_out and pool_out) and cout % 4 == 0
+                and cin % 8 == 0 and self._mx8_cin(cin) and self._mx8_patch_fits(*((2 * hi, 2 * wi) if ups else (hi, wi)))):
+            return "mx8"
+        return "stream3" if ks == 3 else "pointwise"
 
     def conv(self, x, w, bias=None, *, ks, ups=False, relu_in=False, mask=None, res=None, res_ups=False,
              res_scale=1.0, alpha=1.0, out_f32=False, pool_out=False, relu_out=False, mask_after_res=False, valid=0,
@@ -315,9 +383,6 @@ class HipOps:
         spectrally-normalised layer whose prepared weights are a pure cast of W (``fold_sigma``).
         ``x2`` (compact pointwise launches only, xmc_conv2d_pw_dual): a second source (n, h2, w2, c2) whose pixel
         (x2_stride * y, x2_stride * x) is concatenated behind x's channels -- ``w`` then has cin + c2 input channels."""
-        if x2 is not None:
-            return self._conv_pw_dual(x, x2, w, bias, ks=ks, res=res, relu_out=relu_out, valid=valid, emit_bits=emit_bits, compact=compact,
-                                      out=out, x2_stride=x2_stride, alpha=alpha, res_scale=res_scale, mask=mask, mask_after_res=mask_after_res)
         n, hi, wi, cin = x.shape
         packed = isinstance(w, PackedWeight)
         cout = w.cout if packed else w.shape[0]
@@ -329,9 +394,20 @@ class HipOps:
             pool_out, ups = w.phase[0] == "s2in", w.phase[0] == "s2out"
             if pool_out:
                 alpha = 4.0 * alpha                      # the kernel's "in" form carries the 1/4 of the average pooling
+        route = self._conv_route(w, hi, wi, cin, ks=ks, ups=ups, pool_out=pool_out, stride2=stride2, relu_out=relu_out,
+                                 has_res=res is not None, res_ups=res_ups, has_mask=mask is not None, mask_after_res=mask_after_res,
+                                 valid=valid, dual=x2 is not None)
+        phase = "phase" in route
+        assert phase or not stride2, "stride2: see can_stride2"
+        self.last_conv_route = route
+        self.last_conv_phase = phase                     # bench.py: this launch executes 4/9 of the 3x3 formulation's MFMAs
+        self.last_conv_mx8_phase = self.last_conv_mx8_phase_in = False       # ... on the MX-fp8 phase kernels (set by _conv_mx8)
+        if route == "pw_dual":
+            return self._conv_pw_dual(x, x2, w, bias, ks=ks, res=res, relu_out=relu_out, valid=valid, emit_bits=emit_bits, compact=compact,
+                                      out=out, x2_stride=x2_stride, alpha=alpha, res_scale=res_scale, mask=mask, mask_after_res=mask_after_res)
         if packed:
             assert (w.taps, w.cin) == (ks * ks, cin)
-            w = w.data                                   # None: a phase site whose 3x3 copies were never made
+            w = w.phase[1] if phase else w.data          # data None: a phase site whose 3x3 copies were never made
         else:
             assert w.shape[1] == ks * ks and w.shape[2] == cin
         assert x.dtype == self.dtype
@@ -339,23 +415,6 @@ class HipOps:
         if pool_out:
             assert packed and mask is None and not res_ups, "pool_out: see can_pool_out"
             ho, wo = ho // 2, wo // 2                    # shape of y (and of res)
-        # conv3x3(upsample2(.)) / avg_pool2(conv3x3(.)) as four 2x2 convolutions on the low-resolution grid (2.25x fewer MFMAs)
-        phase = (packed and ks == 3 and not (res_ups or mask_after_res or valid) and (stride2 or not relu_out)
-                 and ((ups and res is None and self._phase_ok(wobj, "s2out" if stride2 else "out", hi, wi, True, False))
-                      or (pool_out and mask is None and self._phase_ok(wobj, "s2in" if stride2 else "in", hi, wi, False, True))))
-        assert phase or not stride2, "stride2: see can_stride2"
-        self.last_conv_phase = bool(phase)               # bench.py: this launch executes 4/9 of the 3x3 formulation's MFMAs
-        self.last_conv_mx8_phase = mx8_phase = False     # ... on conv_phase_mx8_kernel (set by _conv_mx8)
-        self.last_conv_mx8_phase_in = mx8_phase_in = False   # ... on conv_phase_in_mx8_kernel (set by _conv_mx8)
-        if phase:
-            w = wobj.phase[1]
-            # the "out" form on MX-fp8 operands (fp8_phase_mx): the weight carries the MX twin of its phase copy and the C side
-            # says the launch is in conv_phase_mx8_kernel's domain; anything else stays on the bf16 phase kernel, as before
-            mx8_phase = bool(self.fp8 and self.fp8_phase_mx and ups and not stride2 and not relu_out and self.dtype == torch.bfloat16
-                             and wobj.phase_mx8 is not None and self._mx8_phase_ok(hi, wi, cin, cout))
-            # ... and the "in" form (fp8_phase_in_mx) likewise on conv_phase_in_mx8_kernel
-            mx8_phase_in = bool(self.fp8 and self.fp8_phase_in_mx and pool_out and not stride2 and not relu_out and self.dtype == torch.bfloat16
-                                and wobj.phase[0] == "in" and wobj.phase_mx8 is not None and self._mx8_phase_in_ok(hi, wi, cin, cout))
         if w is None and packed and wobj.lazy is not None:
             # a phase-only site reached by a launch outside the phase kernels' domain (a switch toggled after the weights were
             # prepared, relu_out / res / valid set, a 2 x 2 grid): make its plain 3x3 copy now, on THIS stream (a fallback: the
@@ -373,44 +432,27 @@ class HipOps:
             y = out
         else:
             y = self.empty((n, ho, wo, cout), torch.float32 if out_f32 else self.dtype)
-        # ... and on a 3x3 launch: tiles entirely inside the canvas margin are skipped and the margin is NOT zeroed (its consumers are
-        # compact pointwise launches that read the valid corner only)
-        compact3 = bool(compact and packed and ks == 3 and valid and not phase and not stride2 and not (ups or pool_out) and not self.fp8)
-        compact = bool(compact and packed and ks == 1 and valid and out is not None and not self.fp8)
         if mask is not None:
             assert mask.shape == y.shape and mask.dtype == self.dtype
         if res is not None:
             assert res.dtype == self.dtype
             assert tuple(res.shape) == ((n, ho // 2, wo // 2, cout) if res_ups else (n, ho, wo, cout))
-        if mx8_phase:
-            return self._conv_mx8(x, wobj, bias, y, ups=True, relu_in=relu_in, mask=mask, res=None, res_ups=False, res_scale=res_scale,
-                                  alpha=alpha, out_f32=out_f32, pool_out=False, emit=emit_mx8, alpha_dev=alpha_dev, relu_out=False,
-                                  emit_bits=emit_bits, phase=True)
-        if mx8_phase_in:
-            return self._conv_mx8(x, wobj, bias, y, ups=False, relu_in=relu_in, mask=None, res=res, res_ups=False, res_scale=res_scale,
-                                  alpha=alpha, out_f32=out_f32, pool_out=True, emit=emit_mx8, alpha_dev=alpha_dev, relu_out=False,
-                                  emit_bits=emit_bits, phase="in")
-        # MX-fp8 where it pays: rows are padded to 64 channels, so a 96-channel input would do 128 channels of work and its
-        # (large, 128^2) tensor would pay the quantisation pass on top -- measured 0.74x the bf16 kernel; those stay bf16
-        if (self.fp8 and not phase and packed and ks == 3 and self.dtype == torch.bfloat16 and not (mask_after_res or valid)
-                and not (relu_out and pool_out)
-                and cout % 4 == 0 and cin % 8 == 0 and ((cin % 64 == 0 and cin >= self.fp8_min_cin) or self.fp8 == "all") and self._mx8_patch_fits(ho * (2 if pool_out else 1), wo * (2 if pool_out else 1))):
-            return self._conv_mx8(x, wobj, bias, y, ups=ups, relu_in=relu_in, mask=mask, res=res, res_ups=res_ups,
-                                  res_scale=res_scale, alpha=alpha, out_f32=out_f32, pool_out=pool_out, emit=emit_mx8, alpha_dev=alpha_dev,
-                                  relu_out=relu_out, emit_bits=emit_bits)
+        if route.startswith("mx8"):
+            # the phase forms take no residual ("out") / no mask ("in"), as the route made sure; relu_out only on the 3x3 kernel
+            return self._conv_mx8(x, wobj, bias, y, ups=ups, relu_in=relu_in, mask=mask, res=res, res_ups=res_ups, res_scale=res_scale,
+                                  alpha=alpha, out_f32=out_f32, pool_out=pool_out, emit=emit_mx8, alpha_dev=alpha_dev,
+                                  relu_out=relu_out, emit_bits=emit_bits, phase={"mx8": False, "mx8_phase_out": True, "mx8_phase_in": "in"}[route])
+        # compact pointwise launches; on a 3x3 launch: tiles entirely inside the canvas margin are skipped and the margin is NOT zeroed
+        # (its consumers are compact pointwise launches that read the valid corner only)
+        compact = bool(compact and valid and not self.fp8 and (route == "pointwise" and out is not None
+                                                               or route == "stream3" and not (ups or pool_out)))
         d = ConvDesc(n, hi, wi, cin, cout, ks, int(ups), int(relu_in), int(res_ups), int(out_f32), self.code,
-                     float(alpha), float(res_scale), int(packed) | (16 if phase else 0) | (32 if phase and not self.phase4 else 0) | (128 if phase and not getattr(self, "px128", True) else 0) | (64 if compact or compact3 else 0) | (256 if packed and getattr(self, "force_tile128", False) else 0) | (512 if packed and getattr(self, "force_tile96", False) else 0) | (1024 if packed and not self.tile64 else 0) | (2048 if packed and not getattr(self, "tile32", True) else 0) | ((getattr(self, "pw_variant", 0) & 15) << 12 if packed else 0),
-                     int(pool_out), int(relu_out), int(mask_after_res), int(valid), int(valid),        # (bit 8: A/B switch, bench_conv.py)
+                     float(alpha), float(res_scale), self._conv_flags(phase, compact) if packed else 0,
+                     int(pool_out), int(relu_out), int(mask_after_res), int(valid), int(valid),
                      alpha_dev.data_ptr() if alpha_dev is not None else None)
-        ws_bytes = self.lib.xmc_conv2d_workspace_bytes(C.byref(d)) if packed and not getattr(self, "no_split_k", False) else 0
+        ws_bytes = self.lib.xmc_conv2d_workspace_bytes(C.byref(d)) if packed and not self.no_split_k else 0
         ws = self.empty((ws_bytes // 4,), torch.float32) if ws_bytes else None      # split-K scratch (few-tile layers)
-        mbits = ybits = None
-        if packed and self.mask_bits and cout % 16 == 0:
-            mb = getattr(mask, "bits", None) if mask is not None else None
-            if mb is not None and not ws_bytes:
-                mbits = mb
-            if emit_bits and not ws_bytes and not out_f32:
-                ybits = torch.empty((n, ho, wo, cout // 16), dtype=torch.int16, device=self.device)
+        mbits, ybits = self._bit_masks(mask, y, cout, emit_bits=emit_bits, out_f32=out_f32, split=bool(ws_bytes)) if packed else (None, None)
         check(self.lib.xmc_conv2d_nhwc_bits(C.byref(d), _p(x), _p(w), _p(bias), _p(mask), _p(res), _p(y), _p(ws), _p(mbits),
                                             _p(ybits), self._stream()), "xmc_conv2d_nhwc_bits")
         if ybits is not None:
@@ -440,7 +482,7 @@ class HipOps:
 
     def pack_mx8(self, w, phase=False):
         """PackedWeight (bf16 fragment order, 9 taps) -> (w8, wscale) in the MX-fp8 fragment order of xmc_conv2d_mx8;
-        ``phase``: of its 16-tap "out"- or "in"-kind phase copy instead (the weights of the w_packed = 1 | 16 launches)"""
+        ``phase``: of its 16-tap "out"- or "in"-kind phase copy instead (the weights of the XMC_CONV_PHASE launches)"""
         assert isinstance(w, PackedWeight) and w.taps == 9 and (not phase or (w.phase is not None and w.phase[0] in ("out", "in")))
         taps = 16 if phase else 9
         nrb, nc64 = (w.cout + 31) // 32, (w.cin + 63) // 64
@@ -452,27 +494,26 @@ class HipOps:
 
     def _mx8_phase_ok(self, hi, wi, cin, cout):
         """is this ``ups`` launch inside conv_phase_mx8_kernel's domain?  (the C side's own test: xmc_conv2d_mx8_phase_supported)"""
-        d = ConvDesc(1, hi, wi, cin, cout, 3, 1, 0, 0, 0, self.code, 1.0, 1.0, 1 | 16, 0, 0, 0, 0, 0)
-        return bool(self.lib.xmc_conv2d_mx8_phase_supported(C.byref(d)))
+        return bool(self.lib.xmc_conv2d_mx8_phase_supported(C.byref(self._geometry_desc(hi, wi, cin, cout, True, False))))
 
     def _mx8_phase_in_ok(self, hi, wi, cin, cout):
         """is this ``pool_out`` launch inside conv_phase_in_mx8_kernel's domain?  (the C side's own test: xmc_conv2d_mx8_phase_in_supported)"""
-        d = ConvDesc(1, hi, wi, cin, cout, 3, 0, 0, 0, 0, self.code, 1.0, 1.0, 1 | 16, 1, 0, 0, 0, 0)
-        return bool(self.lib.xmc_conv2d_mx8_phase_in_supported(C.byref(d)))
+        return bool(self.lib.xmc_conv2d_mx8_phase_in_supported(C.byref(self._geometry_desc(hi, wi, cin, cout, False, True))))
 
     def _with_phase_mx8(self, w):
         """MX-fp8 twin of a freshly prepared "out"-kind (``fp8_phase_mx``) or "in"-kind (``fp8_phase_in_mx``) phase copy, made HERE,
         on the preparing stream, for the reason ``_with_mx8`` gives: never lazily at first use"""
         if (self.fp8 and self.fp8_phase and isinstance(w, PackedWeight) and w.phase is not None
                 and ((self.fp8_phase_mx and w.phase[0] == "out") or (self.fp8_phase_in_mx and w.phase[0] == "in"))
-                and self.dtype == torch.bfloat16 and w.cin % 64 == 0 and w.cin >= self.fp8_min_cin):
+                and self.dtype == torch.bfloat16 and self._mx8_cin(w.cin, strict=True)):
             w.phase_mx8 = self.pack_mx8(w, phase=True)
         return w
 
     @staticmethod
     def _mx8_patch_fits(ho, wo):
-        """the MX-fp8 kernel stages a 256-pixel tile's patch as 5 vectors per pixel in 2,048 slots (conv_stream_mx8.hip): the
-        4x4 maps (16 images per tile, 576 patch pixels) do not fit and stay on the bf16 kernel"""
+        """the MX-fp8 kernel stages a 256-pixel tile's patch as 5 vectors per pixel in 2,048 slots: the 4x4 maps (16 images per
+        tile, 576 patch pixels) do not fit and stay on the bf16 kernel.  A Python MIRROR of a C rule (conv_stream_mx8.hip:
+        mx8_stream_plan(d).fits), kept in step by hand: the ABI has no query for it"""
         wt = min(wo, 64)
         rt = min(256 // wt, ho)
         imgs = 256 // (wt * rt)
@@ -480,14 +521,18 @@ class HipOps:
 
     def takes_mx8(self, cin, taps=9):
         """does a 3x3 convolution with ``cin`` input channels run on the MX-fp8 kernel in this mode?  (the rule of ``conv``)"""
-        return bool(self.fp8) and taps == 9 and self.dtype == torch.bfloat16 and (
-            (cin % 64 == 0 and cin >= self.fp8_min_cin) or self.fp8 == "all")
+        return bool(self.fp8) and taps == 9 and self.dtype == torch.bfloat16 and self._mx8_cin(cin)
+
+    def _mx8_cin(self, c, strict=False):
+        """the MX-fp8 channel rule: whole 64-channel packets and enough channels for the quantisation pass to pay
+        (``fp8_min_cin``); ops.fp8 == "all" waives it for the 3x3 kernel, not (``strict``) where packets are produced ahead of use"""
+        return (c % 64 == 0 and c >= self.fp8_min_cin) or (self.fp8 == "all" and not strict)
 
     def _with_mx8(self, w):
         """MX-fp8 copy of a freshly prepared weight, made HERE -- on the stream that prepared the bf16 copy, which every
         consumer stream already waits for -- and not lazily at first use: the two pullbacks of train_g_d run the same
         dgrad weights on two streams, and a copy made by one would be read by the other before its kernel ran."""
-        if self.fp8 and w.taps == 9 and ((w.cin % 64 == 0 and w.cin >= self.fp8_min_cin) or self.fp8 == "all"):
+        if self.fp8 and w.taps == 9 and self._mx8_cin(w.cin):
             w.mx8 = self.pack_mx8(w)
         return w
 
@@ -506,21 +551,16 @@ class HipOps:
         # (packets of a tensor stored AFTER its ReLU -- tag "relu" -- serve either relu_in: max(., 0) is idempotent)
         x8 = pre[0] if pre is not None and (pre[1] == "relu" or pre[1] == bool(relu_in)) else self.quantize_mx8(x, relu=relu_in)
         d = ConvDesc(n, hi, wi, cin, w.cout, 3, int(ups), 0, int(res_ups), int(out_f32), self.code, float(alpha),
-                     float(res_scale), 1 | (16 if phase else 0), int(pool_out), int(relu_out), 0, 0, 0, alpha_dev.data_ptr() if alpha_dev is not None else None)
+                     float(res_scale), self._conv_flags(phase=bool(phase)), int(pool_out), int(relu_out), 0, 0, 0, alpha_dev.data_ptr() if alpha_dev is not None else None)
         ws_query = self.lib.xmc_conv2d_mx8_phase_in_workspace_bytes if phase == "in" else self.lib.xmc_conv2d_mx8_workspace_bytes
-        ws_bytes = ws_query(C.byref(d)) if not getattr(self, "no_split_k", False) else 0
+        ws_bytes = ws_query(C.byref(d)) if not self.no_split_k else 0
         ws = self.empty((ws_bytes // 4,), torch.float32) if ws_bytes else None
         y8 = None
-        if (emit is not None and not ws_bytes and not out_f32 and w.cout % 64 == 0 and w.cout >= self.fp8_min_cin and self._mx8_patch_fits(y.shape[1], y.shape[2])
+        if (emit is not None and not ws_bytes and not out_f32 and self._mx8_cin(w.cout, strict=True) and self._mx8_patch_fits(y.shape[1], y.shape[2])
                 and not self.fp8_debug & 4):
             y8 = torch.empty((y.numel() // w.cout, w.cout // 64, 80), dtype=torch.uint8, device=self.device)
-        mbits = ybits = None             # ReLU masks as bits, as the bf16 kernel's epilogue reads / writes them (HipOps.conv)
-        if self.mask_bits and w.cout % 16 == 0 and not ws_bytes:
-            mb = getattr(mask, "bits", None) if mask is not None else None
-            if mb is not None and not pool_out:
-                mbits = mb
-            if emit_bits and not out_f32:
-                ybits = torch.empty(tuple(y.shape[:-1]) + (w.cout // 16,), dtype=torch.int16, device=self.device)
+        # ReLU masks as bits, as the bf16 kernel's epilogue reads / writes them (HipOps.conv)
+        mbits, ybits = self._bit_masks(mask, y, w.cout, emit_bits=emit_bits, out_f32=out_f32, split=bool(ws_bytes), read_mask=not pool_out)
         if phase == "in":                # entry points of its own: on xmc_conv2d_mx8 this descriptor stays XMC_EINVAL
             assert mask is None and mbits is None
             check(self.lib.xmc_conv2d_mx8_phase_in_bits(C.byref(d), _p(x8), _p(wmx[0]), _p(wmx[1]), _p(bias), _p(res), _p(y), _p(y8),
@@ -559,8 +599,8 @@ class HipOps:
         assert dw.shape == (cout, ks * ks, cin) and dw.dtype == torch.float32
         assert x.dtype == dy.dtype == self.dtype
         d = WgradDesc(n, hi, wi, cin, cout, ks, int(x_ups), int(x_relu), int(dy_ups), self.code,
-                      int(self.wgrad_variant) | (0 if self.phase_conv else 256) | (0x1000 if overwrite else 0),
-                      float(alpha))                        # bit 8: no phase-decomposed kernel; bit 12: XMC_WGRAD_OVERWRITE
+                      int(self.wgrad_variant) | (0 if self.phase_conv else _lib.XMC_WGRAD_NO_PHASE) | (_lib.XMC_WGRAD_OVERWRITE if overwrite else 0),
+                      float(alpha))
         assert db is None or (db.dtype == torch.float32 and db.numel() == cout)
         ws_bytes = self.lib.xmc_conv2d_wgrad_workspace_bytes(C.byref(d)) if self.deterministic else 0
         if ws_bytes:
@@ -573,7 +613,8 @@ class HipOps:
 
     def wgrad_is_phase(self, x, dy, *, ks, x_ups=False, x_relu=False, dy_ups=False):
         """does xmc_conv2d_wgrad_ws run this launch phase-decomposed (conv_wgrad_phase.hip: 16 instead of 36 products per
-        low-resolution pixel)?  Mirrors xmc_conv2d_wgrad_phase_try's domain; bench.py's FLOP accounting only."""
+        low-resolution pixel)?  A Python MIRROR of a C rule (xmc_conv2d_wgrad_phase_try's domain, conv_wgrad_phase.hip), kept in
+        step by hand: the ABI has no query for it.  bench.py's FLOP accounting only."""
         n, hi, wi, cin = x.shape
         cout = dy.shape[-1]
         if not (self.phase_conv and self.deterministic and self.dtype == torch.bfloat16 and ks == 3) or cin % 32 or cout % 32:
@@ -776,7 +817,7 @@ class HipOps:
         g2, cs = self._gb_rows(gb, n, hc, c)
         y = torch.empty_like(x)
         gp, es = g2.data_ptr(), g2.element_size()
-        if (self.fp8 and x.dtype == torch.bfloat16 and c % 64 == 0 and c >= self.fp8_min_cin and self._mx8_patch_fits(2 * h, 2 * w) and not self.fp8_debug & 2
+        if (self.fp8 and x.dtype == torch.bfloat16 and self._mx8_cin(c, strict=True) and self._mx8_patch_fits(2 * h, 2 * w) and not self.fp8_debug & 2
                 and g2.dtype == torch.float32):
             # config.conv_fp8: every consumer of this tensor is a 3x3 convolution (GenBlock: conv(a), conv(upsample(a))) --
             # the kernel writes its MX-fp8 packets along with the bf16 tensor (the weight gradient still reads bf16)
@@ -920,7 +961,7 @@ class HipOps:
     # --------------------------------------------------------------------------------- attention
     def _attn_mfma(self, region, b, r, t, e):
         """attention_for_g on the matrix cores (attn_mfma.hip): bf16 mode, inside the kernel's domain; XMC_ATTN_MFMA=0: A/B"""
-        return (getattr(self, "attn_mfma", True) and region.dtype == torch.bfloat16
+        return (self.attn_mfma and region.dtype == torch.bfloat16
                 and bool(self.lib.xmc_attn_g_mfma_supported(b, r, t, e)))
 
     def attn_g_sliced(self, region, t):
@@ -1013,7 +1054,7 @@ class HipOps:
     def wl_fused_ok(self, image_feat, t):
         """bf16 mode inside the fused kernels' domain (R == 256, E % 64 == 0); XMC_WL_FUSED=0: A/B against the GEMM path"""
         b, r, e = image_feat.shape
-        return (getattr(self, "wl_fused", True) and image_feat.dtype == torch.bfloat16
+        return (self.wl_fused and image_feat.dtype == torch.bfloat16
                 and bool(self.lib.xmc_wl_fused_supported(b, r, t, e)))
 
     def wl_prep_words(self, words_n):
