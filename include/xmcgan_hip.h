@@ -38,7 +38,7 @@ extern "C" {
 #define XMC_F32 0
 #define XMC_BF16 1
 
-#define XMC_ABI_VERSION 30
+#define XMC_ABI_VERSION 31
 int xmc_abi_version(void);
 
 /* Launch-heuristic knobs -- split-K workgroup targets and tile-selection thresholds whose defaults were A/B'd inside the
@@ -849,6 +849,27 @@ int64_t xmc_segment_sumsq_ws_bytes(const int64_t* segs_host, int32_t nseg);
 int xmc_segment_sumsq(const float* x, int64_t n, const int64_t* segs, const int64_t* segs_host, int32_t nseg, double* sumsq,
                       int32_t* nonfinite, void* ws, int64_t ws_bytes, void* stream);
 int xmc_train_stats(const xmc_train_stats_args* a, void* stream);
+
+/* ---- device-resident dataset cache (config.device_dataset_cache; libml/device_cache.py; csrc/dataset_cache.hip, ABI 31) ----
+ * The cache holds every example once, decoded: img [slots][h][w][3] the resized UNFLIPPED image in [0, 1], emb [slots][s][t][e]
+ * the word embeddings of its s captions, sent [slots][s][e] their sentence features, mlen [slots][s] their lengths (all float32,
+ * device memory, 64-bit offsets throughout).  xmc_cache_gather builds a batch of n examples from a plan of
+ * XMC_CACHE_PLAN_STRIDE int32 per example -- {slot, caption, flip, aug_dy, aug_dx, aug_flip, 0, 0} -- in ONE launch:
+ *   image[i, y, x, :]     = img[slot, y, flip ? w-1-x : x, :]
+ *   image_aug[i, y, x, :] = image[i, r(y + aug_dy - pad, h), r((aug_flip ? w-1-x : x) + aug_dx - pad, w), :]   (skipped when NULL)
+ *                           with r(j, L) = j < 0 ? -j : (j >= L ? 2 (L - 1) - j : j): reflect-pad by `pad`, crop at (aug_dy, aug_dx),
+ *                           then the flip (augmentation.augment_shift / augment)
+ *   embedding[i] = emb[slot, caption]   sentence[i] = sent[slot, caption]   max_len[i] = mlen[slot, caption]
+ * Pure data movement (the outputs are bit copies), one writer per output element, no atomics.  `plan` is the DEVICE copy the
+ * kernel reads, `plan_host` the caller's HOST copy, which this call validates before it launches (xmc_cache_plan_check:
+ * 0 <= slot < slots, 0 <= caption < s, 0 <= aug_dy, aug_dx <= 2 pad, h > pad, w > pad; XMC_EINVAL and nothing runs otherwise);
+ * the kernel clamps what it reads from the device copy to the same ranges.  e % 4 == 0 (caption rows move as 16-byte vectors);
+ * every pointer but mlen / max_len / plan is 16-byte aligned; n <= 65535. */
+#define XMC_CACHE_PLAN_STRIDE 8
+int xmc_cache_plan_check(const int32_t* plan_host, int32_t n, int64_t slots, int32_t s, int32_t h, int32_t w, int32_t pad);
+int xmc_cache_gather(const float* img, const float* emb, const float* sent, const float* mlen, int64_t slots, const int32_t* plan,
+                     const int32_t* plan_host, float* image, float* image_aug, float* embedding, float* sentence, float* max_len,
+                     int32_t n, int32_t h, int32_t w, int32_t s, int32_t t, int32_t e, int32_t pad, void* stream);
 
 #ifdef __cplusplus
 }

@@ -30,6 +30,24 @@ def smooth_image(rng, h, w):
     return np.clip(img, 0, 255).astype(np.uint8)
 
 
+def write_shards(d, examples, nshard, rng):
+    """COCO-shaped train / validation shards in directory ``d`` (640 x 480 PNGs, 5 x 17 x 768 embeddings) -> PNG bytes written"""
+    raw = 0
+    for s in range(nshard):
+        recs = []
+        for _ in range(examples // nshard):
+            img = smooth_image(rng, 480, 640)
+            data = png.encode_rgb(img, np.full(480, 4))         # Paeth rows, like a real encoder would mostly choose
+            raw += len(data)
+            emb = rng.standard_normal((5, 17, 768)).astype(np.float32)
+            recs.append(tfrecord.serialize_example({
+                "image": [data], "image/filename": [b"x.jpg"], "caption/text": [b"a caption"] * 5,
+                "caption/embedding": emb.reshape(-1), "caption/max_len": rng.integers(4, 18, 5).astype(np.int64)}))
+        tfrecord.write_records(os.path.join(d, f"coco2014_train.tfrecord-{s}-of-{nshard}"), recs)
+        tfrecord.write_records(os.path.join(d, f"coco2014_validation.tfrecord-{s}-of-{nshard}"), recs[:2])
+    return raw
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--examples", type=int, default=192)
@@ -42,20 +60,7 @@ def main():
     rng = np.random.default_rng(0)
     with tempfile.TemporaryDirectory() as d:
         t0 = time.perf_counter()
-        nshard = args.shards
-        raw = 0
-        for s in range(nshard):
-            recs = []
-            for _ in range(args.examples // nshard):
-                img = smooth_image(rng, 480, 640)
-                data = png.encode_rgb(img, np.full(480, 4))         # Paeth rows, like a real encoder would mostly choose
-                raw += len(data)
-                emb = rng.standard_normal((5, 17, 768)).astype(np.float32)
-                recs.append(tfrecord.serialize_example({
-                    "image": [data], "image/filename": [b"x.jpg"], "caption/text": [b"a caption"] * 5,
-                    "caption/embedding": emb.reshape(-1), "caption/max_len": rng.integers(4, 18, 5).astype(np.int64)}))
-            tfrecord.write_records(os.path.join(d, f"coco2014_train.tfrecord-{s}-of-{nshard}"), recs)
-            tfrecord.write_records(os.path.join(d, f"coco2014_validation.tfrecord-{s}-of-{nshard}"), recs[:2])
+        raw = write_shards(d, args.examples, args.shards, rng)
         quota = None
         try:                                            # the container's CPU quota (cgroup v2), not the host's core count, bounds the decode rate
             q, per = open("/sys/fs/cgroup/cpu.max").read().split()

@@ -18,7 +18,7 @@ LIB_PATH = os.path.join(_HERE, "libxmcgan_hip.so")
 PROBE_LIB_PATH = os.path.join(_HERE, "libxmc_probe.so")
 
 XMC_F32, XMC_BF16 = 0, 1
-ABI_VERSION = 30
+ABI_VERSION = 31
 
 # xmc_conv_desc.w_packed and xmc_wgrad_desc.variant: the names of include/xmcgan_hip.h (tests/test_conv_geometry.py keeps them equal)
 XMC_CONV_PACKED, XMC_CONV_PHASE, XMC_CONV_PHASE_PER_WG, XMC_CONV_COMPACT, XMC_CONV_NO_PX128 = 0x1, 0x10, 0x20, 0x40, 0x80
@@ -72,6 +72,7 @@ class TrainStatsArgs(C.Structure):   # mirrors xmc_train_stats_args
 
 
 TRAIN_STATS_N = 25                   # XMC_TRAIN_STATS_N
+CACHE_PLAN_STRIDE = 8                 # XMC_CACHE_PLAN_STRIDE
 
 _P, _I, _L, _F = C.c_void_p, C.c_int32, C.c_int64, C.c_float
 
@@ -199,6 +200,8 @@ SIGNATURES = {
     "xmc_segment_sumsq_ws_bytes": [_P, _I],
     "xmc_segment_sumsq": [_P, _L, _P, _P, _I, _P, _P, _P, _L, _P],
     "xmc_train_stats": [_P, _P],
+    "xmc_cache_plan_check": [_P, _I, _L, _I, _I, _I, _I],
+    "xmc_cache_gather": [_P, _P, _P, _P, _L, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P],
 }
 
 # diagnostic probes: include/xmc_probe.h, libxmc_probe.so (csrc_probe/) -- outside the product ABI

@@ -59,6 +59,19 @@ def augment_zoom_crop(x, resize_method: str = "bilinear", zoom_ratio: float = 1.
     return np.ascontiguousarray(_random_crop(y, x.shape, _rng(seed)))
 
 
+def augment_shift_draws(seed=None, w: int = 4, random_flip: bool = True):
+    """(oy, ox, flip) that ``augment(x, seed=seed)`` (method "shift", padding ``w``) applies, without an image: the crop corner
+    in the reflect-padded image and the left-right flip.  Consumes ``seed`` exactly as ``augment`` does -- three child generators,
+    oy then ox from the first (``_random_crop``; their range 0 .. 2 w does not depend on the image size), the flip from the third
+    -- so a plan drawn here and executed elsewhere (libml/device_cache.py) reproduces ``augment`` bit for bit."""
+    s_shift, _, s_flip = _rng(seed).integers(0, 2 ** 63 - 1, size=3).tolist()
+    rng_shift = np.random.Generator(np.random.PCG64(s_shift))                  # = default_rng(s_shift), minus its dispatch
+    oy = int(rng_shift.integers(0, 2 * w + 1))
+    ox = int(rng_shift.integers(0, 2 * w + 1))
+    flip = bool(random_flip and np.random.Generator(np.random.PCG64(s_flip)).random() < 0.5)
+    return oy, ox, flip
+
+
 def augment(x, method: str = _SHIFT, random_flip: bool = True, resize_method: str = "bilinear", seed=None, **kwargs):
     """Randomly augments the input image batch -- augmentation.py:25-70."""
     rng = _rng(seed)

@@ -21,9 +21,11 @@ from . import tfrecord
 from .coco_dataset import COCODataset
 
 
-def _records(files, seed: int, shuffle: bool, shuffle_buffer: int, repeat: bool):
+def _records(files, seed: int, shuffle: bool, shuffle_buffer: int, repeat: bool, read=tfrecord.read_records):
     """(global record index, serialized Example) in reading order: files shuffled per epoch, records through a shuffle
-    buffer (tf.data's ``shuffle(buffer)`` semantics), endless when ``repeat``."""
+    buffer (tf.data's ``shuffle(buffer)`` semantics), endless when ``repeat``.  ``read(path)`` iterates a file's records: the
+    device-resident cache (device_cache.py) passes one that yields the records' cache slots instead of their bytes, so both
+    paths walk the same order with the same draws."""
     rng = np.random.default_rng(seed)
     index = 0
     while True:
@@ -32,7 +34,7 @@ def _records(files, seed: int, shuffle: bool, shuffle_buffer: int, repeat: bool)
             rng.shuffle(order)
         buf = []
         for path in order:
-            for rec in tfrecord.read_records(path):
+            for rec in read(path):
                 buf.append((index, rec))
                 index += 1
                 if len(buf) >= max(1, shuffle_buffer if shuffle else 1):
@@ -43,6 +45,11 @@ def _records(files, seed: int, shuffle: bool, shuffle_buffer: int, repeat: bool)
             return
 
 
+def _record_seed(seed) -> int:
+    """seed of the reading order (``_records``) of the stream whose examples are drawn from ``default_rng([*seed, i])``"""
+    return int(np.random.SeedSequence([int(v) for v in np.atleast_1d(seed)]).generate_state(1)[0])
+
+
 def _examples(ds: COCODataset, files, seed, shuffle: bool, shuffle_buffer: int, repeat: bool, training: bool,
               workers: int = 1):
     """Decoded + augmented examples in record order.  ``seed`` is a sequence of ints (stream, rank): the per-example
@@ -51,7 +58,7 @@ def _examples(ds: COCODataset, files, seed, shuffle: bool, shuffle_buffer: int, 
     inflate / un-filter / resize in C, GIL released) run on a thread pool, ``2 * workers`` records ahead, results kept
     in order (the reference maps with ``num_parallel_calls=AUTOTUNE``, base_dataset.py:69-72)."""
     seed = [int(v) for v in np.atleast_1d(seed)]
-    recs = _records(files, int(np.random.SeedSequence(seed).generate_state(1)[0]), shuffle, shuffle_buffer, repeat)
+    recs = _records(files, _record_seed(seed), shuffle, shuffle_buffer, repeat)
 
     def decode(item):
         i, r = item
@@ -87,10 +94,12 @@ class SlotBatch(dict):
 _ERR = "__xmc_worker_error__"
 
 
-def _mp_worker(q, free_q, ds_kw, files, seed, shuffle, shuffle_buffer, repeat, training, threads, batch, nslots):
+def _mp_worker(q, free_q, ds_kw, files, seed, shuffle, shuffle_buffer, repeat, training, threads, batch, nslots, fill_starts=None):
     """child process of _batches_mp: decode its share of the shards, assemble whole batches and write them into a RING of
     ``nslots`` preallocated shared-memory slots (one segment per worker, created once: no per-batch segment creation, file-
-    descriptor passing or first-touch page faults); only (slot index, non-array fields) travel through the queue."""
+    descriptor passing or first-touch page faults); only (slot index, non-array fields) travel through the queue.
+    ``fill_starts`` (the first cache slot of each of ``files``): the one pass that fills the device-resident cache -- the
+    "batches" are device_cache.fill_chunks' runs of decoded, resized, un-augmented records."""
     shm = None
     try:
         from multiprocessing import shared_memory
@@ -102,7 +111,12 @@ def _mp_worker(q, free_q, ds_kw, files, seed, shuffle, shuffle_buffer, repeat, t
         ds = COCODataset(**ds_kw)
         views = None
         stopped = False                              # the parent's stop token (None on free_q) has been consumed
-        for b in _batches(_examples(ds, files, seed, shuffle, shuffle_buffer, repeat, training, threads), batch):
+        if fill_starts is not None:
+            from . import device_cache
+            source = device_cache.fill_chunks(ds, files, fill_starts, threads, batch)
+        else:
+            source = _batches(_examples(ds, files, seed, shuffle, shuffle_buffer, repeat, training, threads), batch)
+        for b in source:
             arrays = {k: np.ascontiguousarray(v) for k, v in b.items() if isinstance(v, np.ndarray) and k != "image_aug"}
             others = {k: v for k, v in b.items() if not isinstance(v, np.ndarray)}
             # image_aug is a copy of image in this pipeline and is never read by the step (coco_dataset.py:138,156: SURVEY 8a);
@@ -145,7 +159,7 @@ def _mp_worker(q, free_q, ds_kw, files, seed, shuffle, shuffle_buffer, repeat, t
 
 
 def _batches_mp(ds_kw, files, seed, shuffle: bool, shuffle_buffer: int, repeat: bool, training: bool, batch: int, procs: int,
-                threads: int = 2, nslots: int = 4):
+                threads: int = 2, nslots: int = 4, fill_starts=None):
     """Batches from ``procs`` worker PROCESSES (the thread pool of _examples stops scaling at ~8 threads: the Example parse
     and the NumPy glue hold the GIL).  Worker w owns shards ``files[w::procs]`` with its own shuffle buffer and random
     streams ([*seed, w]) and assembles whole batches; the parent takes one batch from each live worker in turn -- a
@@ -162,7 +176,7 @@ def _batches_mp(ds_kw, files, seed, shuffle: bool, shuffle_buffer: int, repeat: 
             fq.put(sl)
         pr = ctx.Process(target=_mp_worker, daemon=True,
                          args=(q, fq, ds_kw, files[w::procs], [*np.atleast_1d(seed).tolist(), w], shuffle, shuffle_buffer,
-                               repeat, training, threads, batch, nslots))
+                               repeat, training, threads, batch, nslots, None if fill_starts is None else fill_starts[w::procs]))
         pr.start()
         qs.append(q)
         fqs.append(fq)
@@ -392,6 +406,16 @@ def create_datasets(config, data_rng: int = 0, rank: int = 0, world: int = 1, de
     requested = procs
     procs, workers_mp = decode_layout(procs, workers, cpu_budget() / max(1, int(os.environ.get("LOCAL_WORLD_SIZE", "1"))),
                                       shards=len(shard("train")))
+    if config.get("device_dataset_cache", False):
+        # decode once, keep the result in HBM (in host arrays without a device) and gather every batch from there: the batches are
+        # those of the procs == 0 path below, bit for bit; the decode layout only sets the parallelism of the one fill pass
+        from . import device_cache
+        fill_threads = max(1, workers_mp if procs > 0 else workers)
+        tr = device_cache.DeviceDatasetCache(ds, shard("train"), device, fill_threads, procs)
+        ev = device_cache.DeviceDatasetCache(ds, shard("val"), device, fill_threads, procs, reserved_bytes=tr.nbytes)
+        return (tr.batches([seed, 0, rank], config.get("train_shuffle", True), sb, True, per_device_train, prefetch),
+                ev.batches([seed, 1, rank], True, sb, True, max(1, config.get("eval_batch_size", per_device) // world), prefetch),
+                ds.num_examples["train"])
     if procs > 0:
         workers = workers_mp
         if requested < 0:                   # the data order follows the process count: say which one this host resolved to

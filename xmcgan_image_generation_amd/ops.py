@@ -43,6 +43,36 @@ def _p(t):
     return C.c_void_p(t.data_ptr())
 
 
+def cache_gather(img, emb, sent, mlen, plan, plan_host, pad=4, with_aug=True):
+    """One batch from the device-resident dataset cache (libml/device_cache.py; ``xmc_cache_gather``): a single launch on the current
+    stream of the cache's device.  img (slots, H, W, 3), emb (slots, S, T, E), sent (slots, S, E), mlen (slots, S): the float32
+    cache; ``plan``: (n, 8) int32 device tensor, ``plan_host``: its host copy (C-contiguous int32 ndarray), which the library
+    validates before it launches -- a plan that would index outside the cache raises XmcError and nothing runs.
+    -> dict(image, [image_aug,] embedding, max_len, sentence_embedding) of fresh tensors.  No HipOps instance is needed: the input
+    pipeline calls this from its own thread and stream."""
+    lib = _lib.load()
+    n = plan.shape[0]
+    slots, h, w, _ = img.shape
+    _, s, t, e = emb.shape
+    assert all(x.dtype == torch.float32 and x.is_cuda and x.device == img.device for x in (img, emb, sent, mlen))
+    assert img.shape[3] == 3 and sent.shape == (slots, s, e) and mlen.shape == (slots, s)
+    assert plan.dtype == torch.int32 and plan.shape == (n, _lib.CACHE_PLAN_STRIDE) and plan.device == img.device
+    assert isinstance(plan_host, np.ndarray) and plan_host.dtype == np.int32 and plan_host.shape == tuple(plan.shape) \
+        and plan_host.flags["C_CONTIGUOUS"]
+    dev = img.device
+    out = dict(image=torch.empty((n, h, w, 3), dtype=torch.float32, device=dev))
+    if with_aug:
+        out["image_aug"] = torch.empty((n, h, w, 3), dtype=torch.float32, device=dev)
+    out["embedding"] = torch.empty((n, t, e), dtype=torch.float32, device=dev)
+    out["max_len"] = torch.empty((n, 1), dtype=torch.float32, device=dev)
+    out["sentence_embedding"] = torch.empty((n, e), dtype=torch.float32, device=dev)
+    stream = C.c_void_p(torch._C._cuda_getCurrentRawStream(dev.index if dev.index is not None else torch.cuda.current_device()))
+    check(lib.xmc_cache_gather(_p(img), _p(emb), _p(sent), _p(mlen), slots, _p(plan), C.c_void_p(plan_host.ctypes.data),
+                               _p(out["image"]), _p(out.get("image_aug")), _p(out["embedding"]), _p(out["sentence_embedding"]),
+                               _p(out["max_len"]), n, h, w, s, t, e, pad, stream), "xmc_cache_gather")
+    return out
+
+
 class PackedWeight:
     """Prepared conv weights in MFMA-fragment order (include/xmcgan_hip.h: xmc_pack_conv_weight)."""
     __slots__ = ("data", "cout", "taps", "cin", "mx8", "phase", "lazy", "phase_mx8")
@@ -949,6 +979,8 @@ class HipOps:
         assert len(segs_host) == 2 * nseg and ws.dtype == torch.uint8
         check(self.lib.xmc_segment_sumsq(_p(x), x.numel(), _p(segs), segs_host, nseg, _p(sumsq), _p(nonfinite), _p(ws), ws.numel(),
                                          self._stream()), "xmc_segment_sumsq")
+
+    cache_gather = staticmethod(cache_gather)        # the dataset cache's batch gather (module-level: needs no operator table)
 
     def train_stats(self, args):
         """one single-workgroup launch of xmc_train_stats on the current stream; ``args``: a filled ``_lib.TrainStatsArgs``"""
