@@ -38,7 +38,7 @@ extern "C" {
 #define XMC_F32 0
 #define XMC_BF16 1
 
-#define XMC_ABI_VERSION 31
+#define XMC_ABI_VERSION 32
 int xmc_abi_version(void);
 
 /* Launch-heuristic knobs -- split-K workgroup targets and tile-selection thresholds whose defaults were A/B'd inside the
@@ -870,6 +870,36 @@ int xmc_cache_plan_check(const int32_t* plan_host, int32_t n, int64_t slots, int
 int xmc_cache_gather(const float* img, const float* emb, const float* sent, const float* mlen, int64_t slots, const int32_t* plan,
                      const int32_t* plan_host, float* image, float* image_aug, float* embedding, float* sentence, float* max_len,
                      int32_t n, int32_t h, int32_t w, int32_t s, int32_t t, int32_t e, int32_t pad, void* stream);
+
+/* ---- pairwise sample metrics: KID and improved precision / recall (config.eval_extra_metrics; utils/sample_metrics.py is the
+ *      specification; csrc/sample_metrics.hip, ABI 32) ----
+ * Pools are row-major float32 [rows][d].  One workgroup owns 128 rows and walks every 128-row tile of the other pool: the dot
+ * products run on the exact-fp32 MFMA (one rounding per product, a k-ordered fmaf chain), everything after them is float64 --
+ * the squared norms (sums of the float32 squares), d2(a, b) = max(0, |a|^2 + |b|^2 - 2 (double)dot), the comparison with a
+ * radius, (dot / d + 1)^3 and every sum.  No n x m matrix is written anywhere; each row's state lives in one thread's registers
+ * and is updated in column order; no atomics: two launches on the same inputs give the same bits.
+ *   xmc_knn_radii:  radii2[i] = the k-th smallest d2(x_i, x_j) over j != i (exclusion by INDEX: a duplicate row is a neighbour at
+ *                   distance 0).  1 <= k <= 8, k < n.
+ *   xmc_ball_hits:  hit[i] = 1 when d2(a_i, b_j) <= radii2_b[j] for some j < m, else 0 (n bytes).  A workgroup stops walking once
+ *                   all its rows are hit (the result does not depend on it).
+ *   xmc_poly3_sums: per subset s < subsets, with X_p = x[xi[s * msub + p]] and Y_q = y[yi[s * msub + q]] (rows gathered through the
+ *                   index arrays, no copies; x and y may be the same buffer) and k(u, v) = (u.v / d + 1)^3:
+ *                   sums[3 s + 0] = sum over p != q of k(X_p, X_q), [3 s + 1] = the same over Y, [3 s + 2] = sum over all p, q of
+ *                   k(X_p, Y_q).  Subsets are the grid's second dimension; every row block leaves a float64 partial in ws and a
+ *                   last kernel adds them in block order.  nx, ny: rows of x and y -- the CALLER validates its host copy of the
+ *                   indices against them before the launch (ops.py); the kernel clamps what it reads from the device copy.
+ * Workspace: xmc_sample_metrics_ws_bytes(n, m, d, subsets) bytes, 16-byte aligned, owned by the caller -- 8 (n + m) for the
+ * squared norms of xmc_knn_radii (m = 0) / xmc_ball_hits, and 24 * subsets * ceil(max(n, m) / 128) for the partials of
+ * xmc_poly3_sums (n = m = msub), whichever is larger; XMC_EINVAL (negative) outside the domain.
+ * Domain: n, m, nx, ny >= 1; d >= 32, d % 32 == 0; 1 <= k <= 8 and k < n; msub >= 2; 1 <= subsets <= 65535; no NULL pointer; every
+ * pointer 16-byte aligned.  Anything else returns XMC_EINVAL and launches nothing.  The caller owns every buffer; the calls are
+ * asynchronous on `stream`. */
+int64_t xmc_sample_metrics_ws_bytes(int32_t n, int32_t m, int32_t d, int32_t subsets);
+int xmc_knn_radii(const float* x, int32_t n, int32_t d, int32_t k, double* radii2, void* ws, void* stream);
+int xmc_ball_hits(const float* a, int32_t n, const float* b, const double* radii2_b, int32_t m, int32_t d, uint8_t* hit, void* ws,
+                  void* stream);
+int xmc_poly3_sums(const float* x, int32_t nx, const int32_t* xi, const float* y, int32_t ny, const int32_t* yi, int32_t subsets,
+                   int32_t msub, int32_t d, double* sums, void* ws, void* stream);
 
 #ifdef __cplusplus
 }

@@ -71,6 +71,11 @@ def get_config() -> ConfigDict:
     c.conv_fp8_phase = False        # with conv_fp8: the "out"-form phase launches (conv3x3(upsample2(.))) on the MX-fp8 phase kernel too
     c.conv_fp8_phase_in = False     # with conv_fp8: the "in"-form phase launches (avg_pool2(conv3x3(.))) on the MX-fp8 "in" phase kernel too
     c.device_dataset_cache = False  # decode every record once, keep it in HBM and gather each batch there (libml/device_cache.py)
+    # evaluation beyond FID / IS (utils/sample_metrics.py; EvalMetric.calculate_metrics): names from {"kid", "precision_recall"}
+    c.eval_extra_metrics = ()
+    c.kid_subsets = 100             # KID: random subsets per pass ...
+    c.kid_subset_size = 1000        # ... of this many rows of each pool
+    c.pr_k = 3                      # precision / recall: a row's ball reaches to its pr_k-th nearest other row
     c.train_statistics = False      # in-graph statistics of train_g_d: head accuracies, D's logits, gradient / parameter norms (train_statistics.py)
     return c
 

@@ -93,6 +93,15 @@ def check_config(config):
     if config.get("conv_fp8_phase_in", False) and not config.get("conv_fp8", False):
         raise ValueError("conv_fp8_phase_in=True needs conv_fp8=True: it moves the in-form phase launches of the MX-fp8 mode "
                          "onto the MX-fp8 \"in\" phase kernel and means nothing in the bf16 mode")
+    extras = tuple(config.get("eval_extra_metrics", ()))
+    if extras:
+        from ..utils.eval_metrics import extra_metric_keys
+        extra_metric_keys(extras)                     # ValueError on a name outside {"kid", "precision_recall"}
+        if "precision_recall" in extras and not 1 <= int(config.get("pr_k", 3)) < int(config.get("eval_num", 30000)):
+            raise ValueError(f"pr_k={config.get('pr_k', 3)} must be at least 1 and below eval_num={config.get('eval_num', 30000)}: "
+                             "a row's radius is the distance to its pr_k-th nearest OTHER row of the pool")
+        if "kid" in extras and (int(config.get("kid_subsets", 100)) < 1 or int(config.get("kid_subset_size", 1000)) < 2):
+            raise ValueError("kid_subsets must be at least 1 and kid_subset_size at least 2")
 
 
 class _Net:

@@ -982,6 +982,76 @@ class HipOps:
 
     cache_gather = staticmethod(cache_gather)        # the dataset cache's batch gather (module-level: needs no operator table)
 
+    # ------------------------------------------------------------------ pairwise sample metrics (utils/sample_metrics.py)
+    def sample_pool(self, x):
+        """an (n, d) float32 pool on this table's device (a NumPy array is uploaded; a device tensor is taken as it is), so that a
+        caller who passes one pool to several of the calls below uploads it once"""
+        if not isinstance(x, torch.Tensor):
+            x = torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32))
+        if x.device != self.device:
+            x = x.to(self.device)
+        assert x.dtype == torch.float32 and x.dim() == 2 and x.is_contiguous()
+        return x
+
+    def _sample_ws(self, n, m, d, subsets):
+        nbytes = self.lib.xmc_sample_metrics_ws_bytes(n, m, d, subsets)
+        check(min(nbytes, 0), "xmc_sample_metrics_ws_bytes")
+        return torch.empty((max(int(nbytes), 16),), dtype=torch.uint8, device=self.device)
+
+    def knn_radii(self, x, k, out=None):
+        """(n,) float64 ndarray: squared distance of every row of the pool ``x`` to its k-th nearest other row (``xmc_knn_radii``;
+        specification: ``sample_metrics.knn_radii_spec``).  ``out``: a float64 device tensor to fill and return instead."""
+        x = self.sample_pool(x)
+        n, d = x.shape
+        radii = torch.empty((n,), dtype=torch.float64, device=self.device) if out is None else out
+        assert radii.dtype == torch.float64 and radii.numel() >= n and radii.is_contiguous()
+        ws = self._sample_ws(n, 0, d, 0)
+        check(self.lib.xmc_knn_radii(_p(x), n, d, int(k), _p(radii), _p(ws), self._stream()), "xmc_knn_radii")
+        return radii.cpu().numpy() if out is None else out
+
+    def ball_hits(self, a, b, radii_b, out=None):
+        """(n,) bool ndarray: is row i of ``a`` within ``radii_b[j]`` (squared) of some row j of ``b`` (``xmc_ball_hits``).
+        ``out``: a uint8 device tensor to fill and return instead."""
+        a, b = self.sample_pool(a), self.sample_pool(b)
+        (n, d), m = a.shape, b.shape[0]
+        assert b.shape[1] == d
+        if not isinstance(radii_b, torch.Tensor):
+            radii_b = torch.from_numpy(np.ascontiguousarray(radii_b, dtype=np.float64))
+        if radii_b.device != self.device:
+            radii_b = radii_b.to(self.device)
+        assert radii_b.dtype == torch.float64 and radii_b.shape == (m,) and radii_b.is_contiguous()
+        hit = torch.empty((n,), dtype=torch.uint8, device=self.device) if out is None else out
+        assert hit.dtype == torch.uint8 and hit.numel() >= n and hit.is_contiguous()
+        ws = self._sample_ws(n, m, d, 0)
+        check(self.lib.xmc_ball_hits(_p(a), n, _p(b), _p(radii_b), m, d, _p(hit), _p(ws), self._stream()), "xmc_ball_hits")
+        return hit.cpu().numpy().astype(bool) if out is None else out
+
+    def poly3_sums(self, x, xi, y, yi, out=None):
+        """(subsets, 3) float64 ndarray of the cubic-kernel sums of KID over the rows ``x[xi[s]]`` and ``y[yi[s]]`` of every subset
+        s (``xmc_poly3_sums``; specification: ``sample_metrics.poly3_sums_spec``).  ``xi`` / ``yi``: (subsets, m) integer HOST
+        arrays, validated here against the pools before anything is launched (ValueError), then uploaded.  ``out``: a float64
+        device tensor to fill and return instead."""
+        x, y = self.sample_pool(x), self.sample_pool(y)
+        host = []
+        for idx, pool, what in ((xi, x, "xi"), (yi, y, "yi")):
+            idx = np.ascontiguousarray(idx)
+            if idx.ndim != 2 or idx.dtype.kind not in "iu":
+                raise ValueError(f"poly3_sums: {what} is a (subsets, m) integer array")
+            if idx.size and (int(idx.min()) < 0 or int(idx.max()) >= pool.shape[0]):
+                raise ValueError(f"poly3_sums: {what} holds an index outside [0, {pool.shape[0]})")
+            host.append(idx.astype(np.int32))
+        if host[0].shape != host[1].shape or x.shape[1] != y.shape[1]:
+            raise ValueError("poly3_sums: pools of one width, index arrays of one shape")
+        subsets, m = host[0].shape
+        d = x.shape[1]
+        dxi, dyi = (torch.from_numpy(h).to(self.device) for h in host)
+        sums = torch.empty((subsets, 3), dtype=torch.float64, device=self.device) if out is None else out
+        assert sums.dtype == torch.float64 and sums.numel() >= 3 * subsets and sums.is_contiguous()
+        ws = self._sample_ws(m, m, d, subsets)
+        check(self.lib.xmc_poly3_sums(_p(x), x.shape[0], _p(dxi), _p(y), y.shape[0], _p(dyi), subsets, m, d, _p(sums), _p(ws),
+                                      self._stream()), "xmc_poly3_sums")
+        return sums.cpu().numpy() if out is None else out
+
     def train_stats(self, args):
         """one single-workgroup launch of xmc_train_stats on the current stream; ``args``: a filled ``_lib.TrainStatsArgs``"""
         check(self.lib.xmc_train_stats(C.byref(args), self._stream()), "xmc_train_stats")

@@ -623,7 +623,9 @@ def test(config, workdir, *, datasets=None, inception_ckpt_path=None, inception=
     """The evaluation loop (reference train_utils.py:464-514): FID and Inception Score, from the current and from the EMA
     parameters, of every checkpoint of ``workdir/checkpoints-0`` that has no row in its ``scores.csv`` yet; waits for new
     checkpoints until ``timeout`` seconds pass without one or ``TRAIN_DONE`` appears.  The eight values go as ``eval/<name>`` to
-    ``scores.csv`` and to ``workdir/metrics.jsonl``.  ``inception`` / ``inception_ckpt_path``: see ``EvalMetric`` (which is built
+    ``scores.csv`` and to ``workdir/metrics.jsonl``; with ``config.eval_extra_metrics`` (``"kid"``, ``"precision_recall"``) so do the
+    values ``EvalMetric.calculate_metrics`` adds.  A ``scores.csv`` that was started with another set of columns raises ValueError
+    before anything is evaluated.  ``inception`` / ``inception_ckpt_path``: see ``EvalMetric`` (which is built
     when the first checkpoint is found).  Returns the number of checkpoints evaluated."""
     import os
     import torch.distributed as dist
@@ -636,6 +638,15 @@ def test(config, workdir, *, datasets=None, inception_ckpt_path=None, inception=
     _, eval_iter, _ = (datasets or default_datasets)(config, streams["data"], 1, rank, world, device)
     manager = task_manager.TaskManagerWithCsvResults(os.path.join(workdir, "checkpoints"), **(task_manager_kw or {}))
     writer = JsonlWriter(os.path.join(workdir, "metrics.jsonl"))
+    extras = tuple(config.get("eval_extra_metrics", ()))
+    keys = EVAL_KEYS + eval_metrics.extra_metric_keys(extras)
+    if os.path.exists(manager.score_file):        # its header was fixed by the first row: a run with other metrics needs another file
+        with open(manager.score_file, newline="") as f:
+            have = sorted(c for c in f.readline().rstrip("\r\n").split(",") if c.startswith("eval/"))
+        want = sorted(f"eval/{k}" for k in keys)
+        if have != want:
+            raise ValueError(f"{manager.score_file} has the columns {have}, this evaluation (eval_extra_metrics={extras}) writes "
+                             f"{want}: move the file away or evaluate with the metrics it was started with")
     eval_metric, done = None, 0
     for path in manager.unevaluated_checkpoints(timeout=timeout):
         if eval_metric is None:
@@ -643,8 +654,12 @@ def test(config, workdir, *, datasets=None, inception_ckpt_path=None, inception=
                                                   chunk=int(config.get("eval_chunk", 256)),
                                                   group=dist.group.WORLD if distributed else None)
         state = checkpoint.restore(path, state)
-        values = eval_metric.calculate_inception_fid(generator, state, streams["eval"])
-        result = {f"eval/{k}": v for k, v in zip(EVAL_KEYS, values)}
+        if extras:
+            values = eval_metric.calculate_metrics(generator, state, streams["eval"])
+            result = {f"eval/{k}": values[k] for k in keys}
+        else:
+            values = eval_metric.calculate_inception_fid(generator, state, streams["eval"])
+            result = {f"eval/{k}": v for k, v in zip(EVAL_KEYS, values)}
         if rank == 0:
             os.makedirs(workdir, exist_ok=True)
             manager.add_eval_result(path, result, -1)

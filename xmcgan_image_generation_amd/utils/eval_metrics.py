@@ -25,7 +25,22 @@ import warnings
 import numpy as np
 import torch
 
-from . import inception_utils
+from . import inception_utils, sample_metrics
+
+# config.eval_extra_metrics: name -> the keys ``EvalMetric.calculate_metrics`` adds for it (mean and std over the passes)
+EXTRA_METRIC_KEYS = {
+    "kid": ("kid", "kid_std", "ema_kid", "ema_kid_std"),
+    "precision_recall": ("precision", "precision_std", "recall", "recall_std",
+                         "ema_precision", "ema_precision_std", "ema_recall", "ema_recall_std"),
+}
+
+
+def extra_metric_keys(names):
+    """the keys ``calculate_metrics`` returns beyond the eight of FID / IS for ``config.eval_extra_metrics = names``"""
+    unknown = [n for n in names if n not in EXTRA_METRIC_KEYS]
+    if unknown:
+        raise ValueError(f"eval_extra_metrics: unknown name(s) {unknown}; known: {sorted(EXTRA_METRIC_KEYS)}")
+    return tuple(k for n in sorted(set(names)) for k in EXTRA_METRIC_KEYS[n])
 
 
 def batch_seed(rng, pass_index, step, rank=0):
@@ -85,10 +100,11 @@ class EvalMetric:
     ``inception_utils.inception_model`` (``None`` = random weights, whose FID means nothing); ``ops``: a ``HipOps`` (default: a
     new one in ``dtype``); ``dtype``: float32 as the reference, bf16 opt-in; ``inception``: any callable
     ``images -> (pool, preds)`` in place of the HIP network; ``chunk``: images per Inception launch sequence; ``group``: a
-    ``torch.distributed`` process group."""
+    ``torch.distributed`` process group; ``metric_ops``: the operator table of the extra metrics (``calculate_metrics``; default:
+    the table Inception runs on, or none -- the NumPy specification -- beside an injected ``inception``)."""
 
     def __init__(self, ds, config, num_splits=1, inception_ckpt_path=None, *, ops=None, dtype=torch.float32, inception=None,
-                 chunk=256, group=None):
+                 chunk=256, group=None, metric_ops=None):
         self.ds = ds
         self.config = config
         self.eval_num = int(config.eval_num)
@@ -107,6 +123,8 @@ class EvalMetric:
             state = inception_utils.inception_model(inception_ckpt_path)
             inception = inception_utils.InceptionV3Features(ops, state["params"], state["batch_stats"])
         self.inception = inception
+        self.metric_ops = metric_ops if metric_ops is not None else ops
+        self._real_radii = {}                     # pr_k -> k-NN radii of the real pool (it never changes)
         self._pool = self._get_real_pool_for_evaluation()
 
     @property
@@ -169,3 +187,45 @@ class EvalMetric:
             ema_fid_list.append(inception_utils.calculate_fid(ema_pool, self._pool))
         return (float(np.mean(fid_list)), float(np.std(fid_list)), float(np.mean(is_list)), float(np.std(is_list)),
                 float(np.mean(ema_fid_list)), float(np.std(ema_fid_list)), float(np.mean(ema_is_list)), float(np.std(ema_is_list)))
+
+    def real_radii(self, k):
+        """squared k-NN radii of the real pool, computed once per ``EvalMetric`` and ``k``"""
+        if k not in self._real_radii:
+            self._real_radii[k] = sample_metrics.knn_radii(self._pool, k, self.metric_ops)
+        return self._real_radii[k]
+
+    def calculate_metrics(self, generator_fn, state, rng):
+        """-> dict: the eight values of ``calculate_inception_fid`` under their ``train_utils.EVAL_KEYS`` names (the same pools, the same
+        arithmetic: bit-equal for the same ``rng``) and, for every name in ``config.eval_extra_metrics``, the mean and std over the
+        passes of KID (``kid``, ``kid_std``) and / or improved precision and recall (``precision``, ``precision_std``, ``recall``,
+        ``recall_std``), each also from the EMA parameters (``ema_`` prefix).  Both are computed from the pools FID uses
+        (``utils/sample_metrics.py``).  The KID subsets of pass i are drawn from ``SeedSequence([rng, i, 0x4B4944])`` and are the same
+        for the current and the EMA pool."""
+        cfg = self.config
+        extras = tuple(cfg.get("eval_extra_metrics", ()))
+        extra_metric_keys(extras)
+        lists = {k: [] for k in ("fid", "is", "ema_fid", "ema_is", "kid", "ema_kid", "precision", "recall", "ema_precision",
+                                 "ema_recall")}
+        for i in range(self.avg_num):
+            pool, preds, ema_pool, ema_preds = self._get_generated_pool_for_evaluation(generator_fn, state, (i, rng))
+            lists["is"].append(inception_utils.calculate_inception_score(preds, num_splits=self.num_splits)[0])
+            lists["ema_is"].append(inception_utils.calculate_inception_score(ema_preds, num_splits=self.num_splits)[0])
+            lists["fid"].append(inception_utils.calculate_fid(pool, self._pool))
+            lists["ema_fid"].append(inception_utils.calculate_fid(ema_pool, self._pool))
+            for prefix, p in (("", pool), ("ema_", ema_pool)):
+                if "kid" in extras:
+                    seed = np.random.SeedSequence([int(rng) & 0xFFFFFFFFFFFFFFFF, i, sample_metrics.KID_SALT])
+                    lists[prefix + "kid"].append(sample_metrics.kid(p, self._pool, int(cfg.get("kid_subsets", 100)),
+                                                                    int(cfg.get("kid_subset_size", 1000)), seed, self.metric_ops)[0])
+                if "precision_recall" in extras:
+                    k = int(cfg.get("pr_k", 3))
+                    pr = sample_metrics.precision_recall(p, self._pool, k, self.metric_ops, real_radii=self.real_radii(k))
+                    lists[prefix + "precision"].append(pr[0])
+                    lists[prefix + "recall"].append(pr[1])
+        out = {}
+        for key, name in (("fid", "fid"), ("inception_score", "is"), ("ema_fid", "ema_fid"), ("ema_inception_score", "ema_is")):
+            out[key], out[key + "_std"] = float(np.mean(lists[name])), float(np.std(lists[name]))
+        for key in extra_metric_keys(extras):
+            if not key.endswith("_std"):
+                out[key], out[key + "_std"] = float(np.mean(lists[key])), float(np.std(lists[key]))
+        return out
