@@ -38,7 +38,7 @@ extern "C" {
 #define XMC_F32 0
 #define XMC_BF16 1
 
-#define XMC_ABI_VERSION 32
+#define XMC_ABI_VERSION 33
 int xmc_abi_version(void);
 
 /* Launch-heuristic knobs -- split-K workgroup targets and tile-selection thresholds whose defaults were A/B'd inside the
@@ -900,6 +900,30 @@ int xmc_ball_hits(const float* a, int32_t n, const float* b, const double* radii
                   void* stream);
 int xmc_poly3_sums(const float* x, int32_t nx, const int32_t* xi, const float* y, int32_t ny, const int32_t* yi, int32_t subsets,
                    int32_t msub, int32_t d, double* sums, void* ws, void* stream);
+
+/* ---- differentiable augmentation of the discriminator's inputs (config.diff_augment; libml/diff_augment.py is the
+ *      specification; csrc/diff_augment.hip, ABI 33) ----
+ * A plan row is eight float32 {b, s, k, ty, tx, y0, x0, c}: brightness shift, saturation and contrast factors, the integer
+ * translation, origin and side of the cutout box (integers as exact floats).  flags: bit 0 brightness, bit 1 saturation, bit 2
+ * contrast; translation and cutout are always applied (a zero shift / a side of 0 is the identity).  Per sample, in float32 with
+ * one rounding on store:
+ *   xmc_diffaug_fwd: u = x + b;  u = (u - mean_c u) s + mean_c u;  u = (u - mu) k + mu with mu = mean_{h,w,c} x + b;
+ *                    out[p] = u[p - t] where p - t lies inside the image and p outside [y0, y0 + c) x [x0, x0 + c), else 0.
+ *                    real, fake: (b, h, w, 3); out: (2b, h, w, 3), the real half first; plan: (2b, 8), rows 0..b-1 the real half.
+ *   xmc_diffaug_bwd: the exact transpose of the linear part on b samples: h[q] = g[q + t] where q + t lies inside the image and
+ *                    outside the box, else 0;  h = k h + (1 - k) mean_{h,w,c} h;  dimg = s h + (1 - s) mean_c h.  g != dimg.
+ * dtype: XMC_F32 or XMC_BF16, of real / fake / out / g / dimg.  `plan` is the DEVICE copy the kernels read, `plan_host` the caller's
+ * HOST copy, validated before anything is launched (every value finite, |ty| < h, |tx| < w, c >= 0; XMC_EINVAL and nothing runs
+ * otherwise); the kernels clamp what they read from the device copy and bounds-check every load.  One launch per call, two with
+ * bit 2 (a fixed-order reduction of the per-sample mean through `workspace`: xmc_diffaug_workspace_bytes(b, h, w) bytes, 4-byte
+ * aligned, may be NULL without bit 2; no atomics).  Rows move as 16-byte vectors when 3 w sizeof(T) is a multiple of 16 and the
+ * image pointers are 16-byte aligned, element by element otherwise.  Domain: 1 <= b, 2 b <= 65535, 1 <= h, w <= 16384,
+ * 3 h w < 2^31, no NULL pointer. */
+int64_t xmc_diffaug_workspace_bytes(int32_t b, int32_t h, int32_t w);
+int xmc_diffaug_fwd(const void* real, const void* fake, const float* plan, const float* plan_host, void* out, int32_t b, int32_t h,
+                    int32_t w, int32_t flags, int32_t dtype, void* workspace, void* stream);
+int xmc_diffaug_bwd(const void* g, const float* plan, const float* plan_host, void* dimg, int32_t b, int32_t h, int32_t w,
+                    int32_t flags, int32_t dtype, void* workspace, void* stream);
 
 #ifdef __cplusplus
 }

@@ -18,7 +18,7 @@ LIB_PATH = os.path.join(_HERE, "libxmcgan_hip.so")
 PROBE_LIB_PATH = os.path.join(_HERE, "libxmc_probe.so")
 
 XMC_F32, XMC_BF16 = 0, 1
-ABI_VERSION = 32
+ABI_VERSION = 33
 
 # xmc_conv_desc.w_packed and xmc_wgrad_desc.variant: the names of include/xmcgan_hip.h (tests/test_conv_geometry.py keeps them equal)
 XMC_CONV_PACKED, XMC_CONV_PHASE, XMC_CONV_PHASE_PER_WG, XMC_CONV_COMPACT, XMC_CONV_NO_PX128 = 0x1, 0x10, 0x20, 0x40, 0x80
@@ -206,6 +206,9 @@ SIGNATURES = {
     "xmc_knn_radii": [_P, _I, _I, _I, _P, _P, _P],
     "xmc_ball_hits": [_P, _I, _P, _P, _I, _I, _P, _P, _P],
     "xmc_poly3_sums": [_P, _I, _P, _P, _I, _P, _I, _I, _I, _P, _P, _P],
+    "xmc_diffaug_workspace_bytes": [_I, _I, _I],
+    "xmc_diffaug_fwd": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P],
+    "xmc_diffaug_bwd": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P],
 }
 
 # diagnostic probes: include/xmc_probe.h, libxmc_probe.so (csrc_probe/) -- outside the product ABI
@@ -219,7 +222,8 @@ PROBE_SIGNATURES = {
 }
 
 _INT64_RETURNS = ("xmc_conv2d_mx8_workspace_bytes", "xmc_conv2d_mx8_phase_in_workspace_bytes", "xmc_conv2d_workspace_bytes", "xmc_bn_stats_ws_floats", "xmc_cbn_bwd_sums_ws_floats",
-                  "xmc_conv2d_wgrad_workspace_bytes", "xmc_reduce_mid_ws_floats", "xmc_gemm_ws_floats", "xmc_segment_sumsq_ws_bytes", "xmc_sample_metrics_ws_bytes")
+                  "xmc_conv2d_wgrad_workspace_bytes", "xmc_reduce_mid_ws_floats", "xmc_gemm_ws_floats", "xmc_segment_sumsq_ws_bytes", "xmc_sample_metrics_ws_bytes",
+                  "xmc_diffaug_workspace_bytes")
 _lib = None
 
 

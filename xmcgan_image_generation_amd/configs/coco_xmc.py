@@ -77,6 +77,9 @@ def get_config() -> ConfigDict:
     c.kid_subset_size = 1000        # ... of this many rows of each pool
     c.pr_k = 3                      # precision / recall: a row's ball reaches to its pr_k-th nearest other row
     c.train_statistics = False      # in-graph statistics of train_g_d: head accuracies, D's logits, gradient / parameter norms (train_statistics.py)
+    # differentiable augmentation of everything D sees (libml/diff_augment.py; not in the reference): a comma-separated subset of
+    # "color", "translation", "cutout"; "" = off, the step is then bit for bit the one without the switch
+    c.diff_augment = ""
     return c
 
 

@@ -982,6 +982,42 @@ class HipOps:
 
     cache_gather = staticmethod(cache_gather)        # the dataset cache's batch gather (module-level: needs no operator table)
 
+    # ------------------------------------------------------------------ differentiable augmentation (libml/diff_augment.py)
+    def _diffaug_args(self, x, plan, plan_host, rows, flags):
+        b, h, w, c = x.shape
+        assert c == 3 and x.is_cuda and x.dtype in (torch.float32, torch.bfloat16)
+        assert plan.dtype == torch.float32 and tuple(plan.shape) == (rows, 8) and plan.device == x.device
+        assert isinstance(plan_host, np.ndarray) and plan_host.dtype == np.float32 and plan_host.shape == (rows, 8) \
+            and plan_host.flags["C_CONTIGUOUS"]
+        ws = None
+        if flags & 4:                                # the contrast step's per-sample mean: partial sums of the first launch
+            nbytes = self.lib.xmc_diffaug_workspace_bytes(b, h, w)
+            check(min(nbytes, 0), "xmc_diffaug_workspace_bytes")
+            ws = self.empty((int(nbytes) // 4,), torch.float32)
+        return b, h, w, ws
+
+    def diff_augment(self, real, fake, plan, plan_host, flags):
+        """The discriminator's augmented input (2B, H, W, 3), real half first, written directly from the two halves
+        (``xmc_diffaug_fwd``; specification: ``diff_augment.apply``).  ``plan``: (2B, 8) float32 device tensor, rows 0..B-1 the real
+        half; ``plan_host``: its host copy (C-contiguous float32 ndarray), validated by the library before it launches -- a bad
+        plan raises XmcError and nothing runs.  One launch on the current stream, two with the contrast bit of ``flags``."""
+        assert real.shape == fake.shape and real.dtype == fake.dtype and fake.device == real.device
+        b, h, w, ws = self._diffaug_args(real, plan, plan_host, 2 * real.shape[0], flags)
+        out = self.empty((2 * b, h, w, 3), real.dtype)
+        check(self.lib.xmc_diffaug_fwd(_p(real), _p(fake), _p(plan), C.c_void_p(plan_host.ctypes.data), _p(out), b, h, w, int(flags),
+                                       _code(real.dtype), _p(ws), self._stream()), "xmc_diffaug_fwd")
+        return out
+
+    def diff_augment_bwd(self, g, plan, plan_host, flags):
+        """d loss / d generated images from d loss / d AUGMENTED generated images ``g`` (B, H, W, 3): the transpose of
+        ``diff_augment`` on the generated half's B plan rows (``xmc_diffaug_bwd``; specification: ``diff_augment.adjoint``).
+        Same shape and dtype as ``g``; one launch on the current stream, two with the contrast bit."""
+        b, h, w, ws = self._diffaug_args(g, plan, plan_host, g.shape[0], flags)
+        dimg = self.empty((b, h, w, 3), g.dtype)
+        check(self.lib.xmc_diffaug_bwd(_p(g), _p(plan), C.c_void_p(plan_host.ctypes.data), _p(dimg), b, h, w, int(flags),
+                                       _code(g.dtype), _p(ws), self._stream()), "xmc_diffaug_bwd")
+        return dimg
+
     # ------------------------------------------------------------------ pairwise sample metrics (utils/sample_metrics.py)
     def sample_pool(self, x):
         """an (n, d) float32 pool on this table's device (a NumPy array is uploaded; a device tensor is taken as it is), so that a

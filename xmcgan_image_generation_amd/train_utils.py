@@ -83,6 +83,8 @@ def create_train_state(config, rng, init_batch=None, ops=None):
     seed; G / D / (unused) z streams are derived from it like the 3-way split of the reference."""
     dtype = torch.bfloat16 if config.dtype == "bfloat16" else torch.float32
     xmc_net.check_config(config)
+    from .libml import diff_augment
+    diff_augment.parse_policy(config.get("diff_augment", ""))     # ValueError on an unknown part, before anything is allocated
     ops = ops if ops is not None else xmc_net.make_ops(dtype)
     if config.get("conv_fp8", False):                # BASELINE config #5: MX-fp8 3x3 convolutions (ops.py::_conv_mx8)
         if dtype != torch.bfloat16:
@@ -132,13 +134,20 @@ def load_flax_params(state, g_params=None, g_batch_stats=None, d_params=None, d_
 
 
 def train_step(rng, state, batch, gan_model=xmc_gan, generator=None, discriminator=None, config=None,
-               additional_data=None, grad_sync=None):
+               additional_data=None, grad_sync=None, d_aug_host=None):
     """One G+D training step (train_utils.py:91-130): the per-device batch (leading dim
-    B * d_step_per_g_step) is split; ``train_d`` runs on the first halves, ``train_g_d`` on the last."""
+    B * d_step_per_g_step) is split; ``train_d`` runs on the first halves, ``train_g_d`` on the last.
+    ``d_aug_host`` (config.diff_augment): the host copy of ``batch["d_aug"]`` when that is a device tensor the caller cannot have
+    read back here (``GraphedTrainStep``'s capture); otherwise it is made from the batch."""
     n = config.d_step_per_g_step
     if grad_sync is not None and config.get("batch_norm_group_size", -1) > 0:
         grad_sync.require_groups(generator(train=True).bn_groups)
     parts = split_input_dict(batch, n)
+    if config.get("diff_augment", "") and "d_aug" in batch and gan_model is xmc_gan:
+        # the plan's host copy rides with each half step's rows: the library validates it before the augmentation launches
+        host = torch.as_tensor(d_aug_host if d_aug_host is not None else xmc_gan.plan_host_of(batch["d_aug"]))
+        for part, rows in zip(parts, torch.chunk(host, n, dim=0)):
+            part["d_aug_host"] = rows
     rngs = [int(rng) * n + i for i in range(n)]      # one stream per half step (train_utils.py:121 splits the key)
     if (gan_model is xmc_gan and xmc_gan._RESNET_REAL_EARLY and grad_sync is None and n > 1 and additional_data
             and additional_data.get("image_model") is not None and config.get("pretrained_image_contrastive", False)):
@@ -198,6 +207,10 @@ class GraphedTrainStep:
             raise ValueError("GraphedTrainStep needs the noise in the batch (key 'z', coco_dataset.py:165-166): a "
                              "host-seeded draw inside train_d / train_g_d cannot be replayed by a captured graph")
         self.static_batch = {k: torch.as_tensor(v).to(dev).clone() for k, v in batch.items()}
+        # config.diff_augment: a capture cannot read the plan back, so its host copy is made here.  It is the CAPTURE-TIME plan:
+        # the library validates it once, while capturing; a replayed plan reaches the kernels through the static tensor only, and
+        # their clamps and bounds checks are what protects a replay
+        aug_host = torch.from_numpy(xmc_gan.plan_host_of(batch["d_aug"]).copy()).pin_memory() if "d_aug" in batch else None
         state = xmc_gan._flush(state)
         bs = g.flat_batch_stats(state.g_optimizer.target, state.generator_state["batch_stats"])
         sn = d.flat_sn_stats(state.d_optimizer.target, state.discriminator_state["spectral_norm_stats"])
@@ -217,7 +230,8 @@ class GraphedTrainStep:
         self.graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(self.graph, capture_error_mode=CAPTURE_ERROR_MODE):
             new_state, metrics = train_step(0, state, self.static_batch, gan_model, generator, discriminator, config,
-                                            additional_data or {}, grad_sync=grad_sync)
+                                            additional_data or {}, grad_sync=grad_sync,
+                                            **({"d_aug_host": aug_host} if aug_host is not None else {}))
             new_state = xmc_gan._flush(new_state)
             bs.flat.copy_(new_state.generator_state["batch_stats"].flat)
             sn.flat.copy_(new_state.discriminator_state["spectral_norm_stats"].flat)
@@ -234,6 +248,9 @@ class GraphedTrainStep:
         # networks' persistent buffers; parameters changed behind the graph's back (load_flax_params, an eager step) are
         # detected by the arenas' version counters and re-prepared eagerly before the replay
         self._nets, self._versions = (g, d), (ga.version, da.version)
+        # the graph reads buffers only ``additional_data`` owns (the frozen ResNet-50's weights and persistent tensors, the
+        # statistics' vectors): they must live as long as the graph does
+        self._additional_data = additional_data
 
     def load_batch(self, batch):
         for k, dst in self.static_batch.items():
@@ -569,9 +586,17 @@ def train(config, workdir, test_mode=False, *, datasets=None):
     statistics = additional_data.get("statistics")   # config.train_statistics: filled by train_g_d, read at the boundaries below
     graphed, window_start = None, initial_step
     n_split = config.d_step_per_g_step
+    from .libml import diff_augment
+    aug_policy = config.get("diff_augment", "")      # differentiable augmentation of D's inputs: a plan per step, like z
     for step in range(initial_step, num_train_steps + 1):
         is_last_step = step == num_train_steps
         batch = {k: v.to(ops.device) for k, v in _array_fields(next(train_iter)).items()}
+        if aug_policy:
+            # a pure function of (seed, step, rank): a resumed run draws what the uninterrupted one did.  Left on the host -- the
+            # eager step validates it there, GraphedTrainStep.load_batch copies it into the graph's static tensor
+            rows, h, w = batch["image"].shape[:3]
+            batch["d_aug"] = torch.from_numpy(diff_augment.draw_plan(fold_in(streams["train"], step), step, rank, rows, h, w,
+                                                                     aug_policy))
         if graphed is None:
             state, metrics = train_step(fold_in(streams["train"], step), state, batch, gan_model, generator, discriminator, config,
                                         additional_data, grad_sync=grad_sync)

@@ -20,6 +20,7 @@ import os
 import torch
 
 from .libml import attention_lib as attn_lib
+from .libml import diff_augment
 from .libml import losses
 from .nets import xmc_net
 from .utils import pretrained_model_utils
@@ -192,6 +193,55 @@ def _same_batch(ident, batch):
             and all(obj is batch[k] and ver == getattr(batch[k], "_version", None) for k, obj, ver in ident))
 
 
+def plan_host_of(aug):
+    """host copy (float32 ndarray) of a ``d_aug`` plan tensor.  A device tensor is read back, which a stream capture does not
+    allow: ``GraphedTrainStep`` makes the copy before it captures and hands it down as ``d_aug_host``."""
+    aug = torch.as_tensor(aug)
+    if aug.is_cuda and torch.cuda.is_current_stream_capturing():
+        raise ValueError("batch['d_aug'] is a device tensor and the stream is capturing: pass its host copy as 'd_aug_host' "
+                         "(GraphedTrainStep does)")
+    return aug.detach().to("cpu", torch.float32).numpy()
+
+
+def _augment_d_input(ops, config, batch, real, img):
+    """D's input under config.diff_augment: ``diff_augment(real, img, batch["d_aug"])`` instead of the concatenation -- on HipOps one
+    kernel that writes the (2B, H, W, 3) buffer from the two halves.  -> (all_images, (plan rows of the generated half on the
+    device, their host copy, flags)) -- all the pullback needs.
+    The host copy is what the library validates before it launches.  Under graph replay only the capture-time plan has been
+    validated that way: the replayed plans arrive in the static device tensor, and the kernels' own clamps and bounds checks are
+    what keeps such a plan from indexing outside a buffer."""
+    flags = diff_augment.parse_policy(config.diff_augment)
+    if "d_aug" not in batch:
+        raise ValueError("config.diff_augment is set but the batch has no 'd_aug' (libml/diff_augment.draw_plan: float32 "
+                         "[rows, 2, 8], drawn per step like 'z')")
+    b = img.shape[0]
+    aug = torch.as_tensor(batch["d_aug"])
+    if tuple(aug.shape) != (b, 2, diff_augment.PLAN_WIDTH):
+        raise ValueError(f"batch['d_aug'] must be ({b}, 2, {diff_augment.PLAN_WIDTH}), got {tuple(aug.shape)}")
+    host = batch["d_aug_host"] if "d_aug_host" in batch else plan_host_of(aug)
+    host = torch.as_tensor(host).to(torch.float32).numpy()
+    host = host.transpose(1, 0, 2).reshape(2 * b, diff_augment.PLAN_WIDTH).copy()      # rows 0..B-1 real, B..2B-1 generated
+    rows = xmc_net._to_dev(ops, aug).transpose(0, 1).reshape(2 * b, diff_augment.PLAN_WIDTH)
+    if hasattr(ops, "diff_augment"):
+        all_images = ops.diff_augment(real.contiguous(), img.contiguous(), rows, host, flags)
+    else:
+        diff_augment.check_plan(host, *img.shape[1:3])                       # (the library's checks, for the torch executors)
+        all_images = diff_augment.apply_torch(torch.cat([real, img], dim=0), rows, flags)
+    return all_images, (rows[b:], host[b:], flags)
+
+
+def _augment_pullback(ops, d_tape, dimg):
+    """d g_loss / d generated images from the gradient ``Discriminator.backward_g`` returns (which, under config.diff_augment, is
+    the one with respect to the AUGMENTED images): the transpose of the augmentation, on the stream this is called on"""
+    ctx = d_tape.get("d_aug")
+    if ctx is None:
+        return dimg
+    rows, host, flags = ctx
+    if hasattr(ops, "diff_augment_bwd"):
+        return ops.diff_augment_bwd(dimg.contiguous(), rows, host, flags)
+    return diff_augment.adjoint_torch(dimg, rows, flags)
+
+
 def _generator_forward(rng, config, state, batch, g, need_tape):
     cond = {k: batch[k] for k in ("sentence_embedding", "embedding", "max_len")}
     if "z" in batch:                                                        # xmc_gan.py:132-136,225-229
@@ -243,7 +293,11 @@ def _forward(rng, config, state, batch, g, d, need_g_tape, image_model=None, aft
         state = _flush(state)
         state.d_optimizer.arena.zero_grads()
     real = ops.cast(xmc_net._to_dev(ops, batch["image"]), ops.dtype)
-    all_images = torch.cat([real, img], dim=0)                               # xmc_gan.py:140,233
+    aug_ctx = None
+    if config.get("diff_augment", ""):       # (not in the reference) the frozen ResNet-50 term below keeps the plain real / img
+        all_images, aug_ctx = _augment_d_input(ops, config, batch, real, img)
+    else:
+        all_images = torch.cat([real, img], dim=0)                           # xmc_gan.py:140,233
     if _ovl(ops, _OVERLAP_PREP) and not deferred and not prep_on_main:
         ops.join_side(d.prepared_tensors() + [t for _, t in _leaves(new_sn)], _PREP_SIDE)
     pre = respre_in if (image_model is not None and respre_in is not None) else None
@@ -262,6 +316,8 @@ def _forward(rng, config, state, batch, g, d, need_g_tape, image_model=None, aft
                                                 **({"want_stats": True} if stats is not None else {}))
     if stats is not None:
         stats.note_forward(logit, loss_vec, d.last_stats, d._sn_ctx[3])
+    if aug_ctx is not None:
+        d_tape["d_aug"] = aug_ctx            # train_g_d pulls the generated half's gradient back through it
     b = img.shape[0]
     hinge = ops.zeros((2,))
     dld, dlg = losses.hinge_loss(ops, logit, b, hinge[0:1], hinge[1:2])      # xmc_gan.py:144-145
@@ -448,7 +504,7 @@ def train_g_d(rng, state, batch, generator, discriminator, config, additional_da
         """pullback (0, 1) down to the generated images: the discriminator's g-stream plus, with
         ``pretrained_image_contrastive``, the frozen ResNet-50 term (xmc_gan.py:148-154)"""
         nonlocal c_pre
-        dimg = d.backward_g(d_tape, dlg_fake)
+        dimg = _augment_pullback(ops, d_tape, d.backward_g(d_tape, dlg_fake))
         if pre is not None:
             c_pre, pull = _pretrained_loss(ops, *pre, b)
             ops.add_into(dimg, pull())
@@ -468,7 +524,7 @@ def train_g_d(rng, state, batch, generator, discriminator, config, additional_da
             # for their whole length instead of [g-stream + ResNet + G] against [D] alone
             ops.join_side(_leaf_tensors(pre[2]) + [pre[1]])                  # the ResNet forward ran on the side stream (_forward)
             with ops.side():
-                dimg = d.backward_g(d_tape, dlg_f)                           # pullback (0, 1), D part
+                dimg = _augment_pullback(ops, d_tape, d.backward_g(d_tape, dlg_f))   # pullback (0, 1), D part
                 if grad_sync is None and _EARLY_ADAM_D:
                     d_part_done = ops.record_event()
             if _RESNET_BWD_MAIN == 2:                                        # A/B: on a THIRD stream, beside D's backward pass as well
