@@ -38,7 +38,7 @@ extern "C" {
 #define XMC_F32 0
 #define XMC_BF16 1
 
-#define XMC_ABI_VERSION 33
+#define XMC_ABI_VERSION 34
 int xmc_abi_version(void);
 
 /* Launch-heuristic knobs -- split-K workgroup targets and tile-selection thresholds whose defaults were A/B'd inside the
@@ -924,6 +924,63 @@ int xmc_diffaug_fwd(const void* real, const void* fake, const float* plan, const
                     int32_t w, int32_t flags, int32_t dtype, void* workspace, void* stream);
 int xmc_diffaug_bwd(const void* g, const float* plan, const float* plan_host, void* dimg, int32_t b, int32_t h, int32_t w,
                     int32_t flags, int32_t dtype, void* workspace, void* stream);
+
+/* ---- CLIP dual encoder and the text-image alignment scores (config.eval_extra_metrics "clip"; utils/clip_utils.py,
+ *      utils/alignment_metrics.py is the specification of the scores and of the preprocessing; csrc/clip.hip, ABI 34) ----
+ * The transformers.CLIPModel network: a ViT image tower and a causal text tower of pre-LN blocks (LN, fused q | k | v product,
+ * attention, out-projection, residual, LN, fc1, QuickGELU, fc2, residual), LayerNorm eps 1e-5, head dimension 64.  Everything
+ * is float32 on activations [rows = n * t][h]; the dense layers are xmc_gemm_f32 / xmc_gemm_f32_bf16mfma on the (out, in)
+ * weights and their biases are added by the kernels below.  Cross-lane reductions are fixed xor trees and nothing is
+ * accumulated with atomics: two launches on the same inputs give the same bits, and no sequence depends on what shares its
+ * launch.  Pointers are 16-byte aligned; XMC_EINVAL otherwise and for every size outside the stated domain (nothing is
+ * launched).  LayerNorm rows: h % 4 == 0, h <= 1024, biased variance as mean((v - mean)^2) over the row held in registers.
+ *
+ *  - xmc_clip_preprocess: images (n, hw, hw, 3), dtype XMC_F32 or XMC_BF16, values in [0, 1] -> the s x s separable Keys cubic
+ *    resize (a = -0.5) with Pillow's BICUBIC rule: the support is 2 max(1, hw / s) input pixels around (o + 0.5) hw / s, the
+ *    window is clipped to the image and the weights (computed in double, rounded to float32) are normalised per output pixel;
+ *    then (v - mean3[c]) / std3[c] (HOST arrays of three floats, std3 > 0).  No uint8 round trip (OpenAI's preprocessing
+ *    quantises the resized image to bytes; this one does not).  Output: patches (n * (s / p)^2, 3 p p), row = image, patch row,
+ *    patch column, column = (c, ky, kx) -- the flattened patch-embedding weight's order, so the patch convolution is one GEMM.
+ *    Domain: 32 <= hw <= 512, p >= 1, s % p == 0, s <= 448.
+ *  - xmc_clip_vision_embed: y[i, 0] = LN(cls + pos[0]), y[i, 1 + j] = LN(patch[i, j] + pos[1 + j]) for j < t - 1 (pre_layrnorm);
+ *    patch (n * (t - 1), h), pos (t, h), y (n * t, h), t >= 2.
+ *  - xmc_clip_text_embed: x[r] = tok[ids[r]] + pos[r mod t]; tok (vocab, h), pos (npos, h), t <= npos.  The CALLER checks
+ *    0 <= ids[r] < vocab on the host before the launch; the kernel clamps an id into the table.
+ *  - xmc_bias_add_ln: s[r] = x[r] + bias + res[r] and y[r] = LayerNorm(s[r]) * gamma + beta.  bias and res may be NULL (terms
+ *    left out: with both NULL this is plain LayerNorm), s may be NULL (not written) or alias res; y may alias x, never s.
+ *  - xmc_bias_quick_gelu: y = v sigmoid(1.702 v) = v / (1 + exp(-1.702 v)), v = x + bias[column], evaluated in float64 and
+ *    rounded once.  x, y (rows, f), f % 4 == 0; y may be x.
+ *  - xmc_mha_attention: qkv (n * t, 3 h) = the fused product [q | k | v] WITHOUT its bias, bias_qkv (3 h), ctx (n * t, h).  Per
+ *    sequence and head: ctx = softmax_j((q + b_q)(k + b_k)^T / 8)(v + b_v) over the keys j < len[i], and with causal != 0 also
+ *    j <= query row; all t query rows are computed.  One 256-thread workgroup per (sequence, head), k and v rows and the
+ *    probabilities [t][t + 1] in LDS (135,680 bytes at t = 128).  Domain: 1 <= len[i] <= t <= 128, h % 64 == 0.  len (DEVICE,
+ *    int32 [n]) is what the kernel reads; len_host is the caller's HOST copy, validated before the launch; the kernel clamps
+ *    what it reads to [1, t].
+ *  - xmc_gather_rows_ln: y[i] = LayerNorm(x[i * t + idx[i]]) * gamma + beta; x (n * t, h), y (n, h).  idx (DEVICE int32 [n]) and
+ *    idx_host (its HOST copy, validated: 0 <= idx < t) are both NULL for row 0 of every sequence (the image tower's class row);
+ *    with idx = the end-of-text positions this is the text tower's pooled row.  The kernel clamps what it reads.
+ *  - xmc_pair_cosine: cos[i] = a[i].b[i] / (|a[i]| |b[i]|) as float64, a, b (n, d): the float32 values multiplied and added in
+ *    float64 -- lane l of the row's wave adds elements l, l + 64, .. in index order, then a fixed xor tree.  A zero row gives 0.
+ *  - xmc_rprecision_hits: img (n, d), txt (m, d), truth int32 [n], cand int32 [n, c]: hit[i] = 1 iff the cosine of (img[i],
+ *    txt[truth[i]]) is STRICTLY greater than that of (img[i], txt[cand[i, j]]) for every j < c, else 0 (n bytes); the arithmetic
+ *    of xmc_pair_cosine.  A candidate that duplicates the true caption ties with it and makes the row a miss.  truth / cand are
+ *    the DEVICE copies, truth_host / cand_host the HOST copies, validated before the launch (0 <= . < m); the kernel clamps. */
+int xmc_clip_preprocess(const void* images, float* patches, int32_t n, int32_t hw, int32_t s, int32_t p, const float* mean3,
+                        const float* std3, int32_t dtype, void* stream);
+int xmc_clip_vision_embed(const float* patch, const float* cls, const float* pos, const float* gamma, const float* beta, float* y,
+                          int32_t n, int32_t t, int32_t h, float eps, void* stream);
+int xmc_clip_text_embed(const int32_t* ids, const float* tok, const float* pos, float* x, int32_t rows, int32_t t, int32_t h,
+                        int32_t vocab, int32_t npos, void* stream);
+int xmc_bias_add_ln(const float* x, const float* bias, const float* res, const float* gamma, const float* beta, float* s, float* y,
+                    int32_t rows, int32_t h, float eps, void* stream);
+int xmc_bias_quick_gelu(const float* x, const float* bias, float* y, int32_t rows, int32_t f, void* stream);
+int xmc_mha_attention(const float* qkv, const float* bias_qkv, const int32_t* len, const int32_t* len_host, float* ctx, int32_t n,
+                      int32_t t, int32_t h, int32_t causal, void* stream);
+int xmc_gather_rows_ln(const float* x, const int32_t* idx, const int32_t* idx_host, const float* gamma, const float* beta, float* y,
+                       int32_t n, int32_t t, int32_t h, float eps, void* stream);
+int xmc_pair_cosine(const float* a, const float* b, double* cos, int32_t n, int32_t d, void* stream);
+int xmc_rprecision_hits(const float* img, const float* txt, const int32_t* truth, const int32_t* truth_host, const int32_t* cand,
+                        const int32_t* cand_host, uint8_t* hit, int32_t n, int32_t m, int32_t d, int32_t c, void* stream);
 
 #ifdef __cplusplus
 }

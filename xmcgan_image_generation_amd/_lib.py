@@ -18,7 +18,7 @@ LIB_PATH = os.path.join(_HERE, "libxmcgan_hip.so")
 PROBE_LIB_PATH = os.path.join(_HERE, "libxmc_probe.so")
 
 XMC_F32, XMC_BF16 = 0, 1
-ABI_VERSION = 33
+ABI_VERSION = 34
 
 # xmc_conv_desc.w_packed and xmc_wgrad_desc.variant: the names of include/xmcgan_hip.h (tests/test_conv_geometry.py keeps them equal)
 XMC_CONV_PACKED, XMC_CONV_PHASE, XMC_CONV_PHASE_PER_WG, XMC_CONV_COMPACT, XMC_CONV_NO_PX128 = 0x1, 0x10, 0x20, 0x40, 0x80
@@ -196,6 +196,15 @@ SIGNATURES = {
     "xmc_bert_attention": [_P, _P, _P, _P, _P, _I, _I, _I, _P],
     "xmc_bert_attention_long": [_P, _P, _P, _P, _P, _I, _I, _I, _P],
     "xmc_bert_sentence": [_P, _P, _P, _I, _I, _I, _P],
+    "xmc_clip_preprocess": [_P, _P, _I, _I, _I, _I, _P, _P, _I, _P],
+    "xmc_clip_vision_embed": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _F, _P],
+    "xmc_clip_text_embed": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P],
+    "xmc_bias_add_ln": [_P, _P, _P, _P, _P, _P, _P, _I, _I, _F, _P],
+    "xmc_bias_quick_gelu": [_P, _P, _P, _I, _I, _P],
+    "xmc_mha_attention": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _P],
+    "xmc_gather_rows_ln": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _F, _P],
+    "xmc_pair_cosine": [_P, _P, _P, _I, _I, _P],
+    "xmc_rprecision_hits": [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P],
     "xmc_metrics_accum": [_P, _I, _P, _P, _P],
     "xmc_segment_sumsq_ws_bytes": [_P, _I],
     "xmc_segment_sumsq": [_P, _L, _P, _P, _I, _P, _P, _P, _L, _P],

@@ -71,11 +71,18 @@ def get_config() -> ConfigDict:
     c.conv_fp8_phase = False        # with conv_fp8: the "out"-form phase launches (conv3x3(upsample2(.))) on the MX-fp8 phase kernel too
     c.conv_fp8_phase_in = False     # with conv_fp8: the "in"-form phase launches (avg_pool2(conv3x3(.))) on the MX-fp8 "in" phase kernel too
     c.device_dataset_cache = False  # decode every record once, keep it in HBM and gather each batch there (libml/device_cache.py)
-    # evaluation beyond FID / IS (utils/sample_metrics.py; EvalMetric.calculate_metrics): names from {"kid", "precision_recall"}
+    # evaluation beyond FID / IS (utils/sample_metrics.py, utils/alignment_metrics.py; EvalMetric.calculate_metrics): names from
+    # {"kid", "precision_recall", "clip"}
     c.eval_extra_metrics = ()
     c.kid_subsets = 100             # KID: random subsets per pass ...
     c.kid_subset_size = 1000        # ... of this many rows of each pool
     c.pr_k = 3                      # precision / recall: a row's ball reaches to its pr_k-th nearest other row
+    # "clip": CLIPScore and R-precision on a CLIP ViT-B/32 (utils/clip_utils.py); all inert unless "clip" is named
+    c.clip_ckpt_path = None         # np.savez of a Hugging Face CLIPModel.state_dict() (None: random weights, meaningless scores)
+    c.clip_vocab_path = None        # CLIP's vocab.json ...
+    c.clip_merges_path = None       # ... and merges.txt (required with "clip")
+    c.clip_fast = False             # bf16 MFMA for the encoder's dense layers
+    c.r_precision_candidates = 99   # mismatched captions every image's own caption has to beat
     c.train_statistics = False      # in-graph statistics of train_g_d: head accuracies, D's logits, gradient / parameter norms (train_statistics.py)
     # differentiable augmentation of everything D sees (libml/diff_augment.py; not in the reference): a comma-separated subset of
     # "color", "translation", "cutout"; "" = off, the step is then bit for bit the one without the switch

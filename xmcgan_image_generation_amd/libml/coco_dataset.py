@@ -25,10 +25,14 @@ class COCODataset:
 
     def __init__(self, image_size: int = 128, z_dim: int = 128, data_dtype=np.float32, data_dir: str = "data/",
                  coco_version: str = "2014", return_text: bool = False, return_filename: bool = False,
-                 sentence_num: int = 5, max_text_length: int = syn.MAX_WORDS, embedding_dim: int = syn.EMB_DIM):
+                 sentence_num: int = 5, max_text_length: int = syn.MAX_WORDS, embedding_dim: int = syn.EMB_DIM,
+                 return_caption_text: bool = False):
         self.image_size, self.z_dim, self.data_dtype = image_size, z_dim, data_dtype
         self.data_dir, self.coco_version = data_dir, coco_version
         self.return_text, self.return_filename = return_text, return_filename
+        # the text of the caption the sampler DREW, next to its embedding (the alignment metrics); unlike return_text it changes
+        # nothing else about the example
+        self.return_caption_text = return_caption_text
         if coco_version == "ln":                     # Localized Narratives: one 64-token caption per image (coco_dataset.py:56-62)
             sentence_num, max_text_length = 1, syn.LN_MAX_WORDS
         self.sentence_num = sentence_num
@@ -84,6 +88,12 @@ class COCODataset:
                    max_len=max_len[idx].astype(dt), sentence_embedding=sentence_feat[idx].astype(dt))
         if self.return_text:
             out["text"] = features["caption/text"][idx]
+        elif self.return_caption_text:
+            texts = features["caption/text"]
+            if idx >= len(texts):
+                raise ValueError(f"the record stores {len(texts)} caption text(s), caption {idx} was drawn: caption/text is missing "
+                                 "or shorter than caption/embedding")
+            out["text"] = texts[idx]
         if self.return_filename:
             out["filename"] = features["image/filename"]
         out["z"] = rng_z.standard_normal((self.z_dim,)).astype(dt)

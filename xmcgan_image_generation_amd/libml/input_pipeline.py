@@ -386,6 +386,18 @@ def create_datasets(config, data_rng: int = 0, rank: int = 0, world: int = 1, de
     ds = COCODataset(image_size=config.image_size, z_dim=config.z_dim, data_dtype=dtype,
                      data_dir=config.get("data_dir", "data/"), coco_version=config.get("coco_version", "2014"),
                      return_text=config.get("return_text", False), return_filename=config.get("return_filename", False))
+    # the alignment metrics read the text of the caption each evaluation example drew (EvalMetric, "clip"); the training stream
+    # and every other field of the evaluation stream are what they are without it
+    caption_text = "clip" in tuple(config.get("eval_extra_metrics", ()))
+    if caption_text and config.get("device_dataset_cache", False):
+        raise ValueError('eval_extra_metrics "clip" is not supported with device_dataset_cache=True: the cache-backed evaluation '
+                         "iterator does not carry the drawn caption's text; evaluate with device_dataset_cache=False")
+    ds_eval = ds
+    if caption_text:
+        ds_eval = COCODataset(image_size=config.image_size, z_dim=config.z_dim, data_dtype=dtype,
+                              data_dir=config.get("data_dir", "data/"), coco_version=config.get("coco_version", "2014"),
+                              return_text=config.get("return_text", False), return_filename=config.get("return_filename", False),
+                              return_caption_text=True)
     seed = int(data_rng)
     if workers is None:
         workers = int(config.get("num_decode_workers", 4))
@@ -427,6 +439,6 @@ def create_datasets(config, data_rng: int = 0, rank: int = 0, world: int = 1, de
     else:
         train = _batches(_examples(ds, shard("train"), [seed, 0, rank], config.get("train_shuffle", True), sb, True, True,
                                    workers), per_device_train)
-    evalb = _batches(_examples(ds, shard("val"), [seed, 1, rank], True, sb, True, False, workers),
+    evalb = _batches(_examples(ds_eval, shard("val"), [seed, 1, rank], True, sb, True, False, workers),
                      max(1, config.get("eval_batch_size", per_device) // world))
     return (Prefetcher(train, prefetch, device), Prefetcher(evalb, prefetch, device), ds.num_examples["train"])

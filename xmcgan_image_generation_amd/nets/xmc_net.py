@@ -96,12 +96,18 @@ def check_config(config):
     extras = tuple(config.get("eval_extra_metrics", ()))
     if extras:
         from ..utils.eval_metrics import extra_metric_keys
-        extra_metric_keys(extras)                     # ValueError on a name outside {"kid", "precision_recall"}
+        extra_metric_keys(extras)                     # ValueError on a name outside {"clip", "kid", "precision_recall"}
         if "precision_recall" in extras and not 1 <= int(config.get("pr_k", 3)) < int(config.get("eval_num", 30000)):
             raise ValueError(f"pr_k={config.get('pr_k', 3)} must be at least 1 and below eval_num={config.get('eval_num', 30000)}: "
                              "a row's radius is the distance to its pr_k-th nearest OTHER row of the pool")
         if "kid" in extras and (int(config.get("kid_subsets", 100)) < 1 or int(config.get("kid_subset_size", 1000)) < 2):
             raise ValueError("kid_subsets must be at least 1 and kid_subset_size at least 2")
+        if "clip" in extras:
+            if not config.get("clip_vocab_path", None) or not config.get("clip_merges_path", None):
+                raise ValueError('eval_extra_metrics "clip" needs clip_vocab_path and clip_merges_path (CLIP\'s vocab.json and '
+                                 "merges.txt; INTEGRATION.md): nothing is downloaded")
+            if int(config.get("r_precision_candidates", 99)) < 1:
+                raise ValueError(f"r_precision_candidates={config.get('r_precision_candidates')} must be at least 1")
 
 
 class _Net:

@@ -1812,6 +1812,129 @@ class HipOps:
         check(self.lib.xmc_bert_sentence(_p(emb), _p(max_len), _p(out), n, t, h, self._stream()), "xmc_bert_sentence")
         return out
 
+    # ------------------------------------- CLIP dual encoder and the alignment scores (utils/clip_utils.py, utils/alignment_metrics.py)
+    def clip_preprocess(self, images, size, patch, mean, std, out=None):
+        """(n, hw, hw, 3) float32 / bf16 in [0, 1] -> normalised patch rows (n * (size / patch)^2, 3 * patch^2) float32
+        (``xmc_clip_preprocess``; specification: ``alignment_metrics.preprocess``)"""
+        n, hw, w, c = images.shape
+        assert hw == w and c == 3 and images.is_contiguous() and images.dtype in (torch.float32, torch.bfloat16)
+        g = size // patch
+        out = self.empty((n * g * g, 3 * patch * patch), torch.float32) if out is None else out
+        assert out.dtype == torch.float32 and out.shape == (n * g * g, 3 * patch * patch) and out.is_contiguous()
+        m3, s3 = (np.ascontiguousarray(v, dtype=np.float32) for v in (mean, std))
+        assert m3.shape == s3.shape == (3,)
+        check(self.lib.xmc_clip_preprocess(_p(images), _p(out), n, hw, int(size), int(patch), C.c_void_p(m3.ctypes.data),
+                                           C.c_void_p(s3.ctypes.data), _code(images.dtype), self._stream()), "xmc_clip_preprocess")
+        return out
+
+    def clip_vision_embed(self, patch, cls, pos, gamma, beta, out, t, eps=1e-5):
+        """out[i, 0] = LN(cls + pos[0]), out[i, 1 + j] = LN(patch[i, j] + pos[1 + j]); out (n * t, h) float32"""
+        rows, h = out.shape
+        n = rows // t
+        assert rows == n * t and patch.shape == (n * (t - 1), h) and pos.shape == (t, h) and cls.numel() == h
+        assert patch.dtype == out.dtype == torch.float32 and patch.is_contiguous() and out.is_contiguous() and pos.is_contiguous()
+        check(self.lib.xmc_clip_vision_embed(_p(patch), _p(cls), _p(pos), _p(gamma), _p(beta), _p(out), n, t, h, float(eps),
+                                             self._stream()), "xmc_clip_vision_embed")
+        return out
+
+    def clip_text_embed(self, ids, tok, pos, out, t):
+        """out[r] = tok[ids[r]] + pos[r mod t]; ids int32 (rows,) ALREADY range-checked by the caller"""
+        rows, h = out.shape
+        assert ids.dtype == torch.int32 and ids.numel() == rows and out.dtype == tok.dtype == torch.float32
+        assert tok.shape[1] == pos.shape[1] == h and out.is_contiguous() and tok.is_contiguous() and pos.is_contiguous()
+        check(self.lib.xmc_clip_text_embed(_p(ids), _p(tok), _p(pos), _p(out), rows, t, h, tok.shape[0], pos.shape[0],
+                                           self._stream()), "xmc_clip_text_embed")
+        return out
+
+    def bias_add_ln(self, x, bias, res, gamma, beta, s=None, out=None, eps=1e-5):
+        """s <- x + bias + res (when ``s`` is given; it may be ``res``), out <- LN(x + bias + res) * gamma + beta over the last dim of
+        (rows, h) float32; ``bias`` / ``res`` may be None"""
+        rows, h = x.shape
+        out = self.empty(x.shape, torch.float32) if out is None else out
+        for t_ in (res, s, out):
+            assert t_ is None or (t_.dtype == torch.float32 and t_.shape == x.shape and t_.is_contiguous())
+        assert x.dtype == torch.float32 and x.is_contiguous() and gamma.numel() == beta.numel() == h
+        assert bias is None or bias.numel() == h
+        null = C.c_void_p(None)
+        check(self.lib.xmc_bias_add_ln(_p(x), null if bias is None else _p(bias), null if res is None else _p(res), _p(gamma), _p(beta),
+                                       null if s is None else _p(s), _p(out), rows, h, float(eps), self._stream()), "xmc_bias_add_ln")
+        return out
+
+    def bias_quick_gelu(self, x, bias, out=None):
+        """v * sigmoid(1.702 v), v = x + bias, (rows, f) float32; ``out`` may be ``x``"""
+        rows, f = x.shape
+        out = self.empty(x.shape, torch.float32) if out is None else out
+        assert x.dtype == out.dtype == torch.float32 and out.shape == x.shape and x.is_contiguous() and out.is_contiguous()
+        assert bias.numel() == f
+        check(self.lib.xmc_bias_quick_gelu(_p(x), _p(bias), _p(out), rows, f, self._stream()), "xmc_bias_quick_gelu")
+        return out
+
+    def mha_attention(self, qkv, bias_qkv, lens, lens_host, ctx, t, causal=False):
+        """ctx (n * t, h) <- multi-head attention of the fused product qkv (n * t, 3 h) (bias added inside) over the keys
+        j < lens[i] (and j <= query row when ``causal``), 1 <= t <= 128; ``lens``: int32 (n,) on the device, ``lens_host``: the same
+        values on the host (validated by the library before the launch)"""
+        rows, h3 = qkv.shape
+        n, h = rows // t, h3 // 3
+        lh = np.ascontiguousarray(lens_host, dtype=np.int32)
+        assert rows == n * t and h3 == 3 * h and ctx.shape == (rows, h) and qkv.is_contiguous() and ctx.is_contiguous()
+        assert qkv.dtype == ctx.dtype == torch.float32 and lens.dtype == torch.int32 and lens.numel() == n == lh.size
+        assert bias_qkv.numel() == h3
+        check(self.lib.xmc_mha_attention(_p(qkv), _p(bias_qkv), _p(lens), C.c_void_p(lh.ctypes.data), _p(ctx), n, t, h,
+                                         int(bool(causal)), self._stream()), "xmc_mha_attention")
+        return ctx
+
+    def gather_rows_ln(self, x, idx, idx_host, gamma, beta, t, out=None, eps=1e-5):
+        """(n * t, h) -> (n, h): LN(x[i * t + idx[i]]) * gamma + beta; ``idx`` int32 (n,) on the device with its host copy
+        ``idx_host``, or both None for row 0 of every sequence"""
+        rows, h = x.shape
+        n = rows // t
+        out = self.empty((n, h), torch.float32) if out is None else out
+        assert rows == n * t and x.dtype == out.dtype == torch.float32 and out.shape == (n, h) and x.is_contiguous()
+        assert (idx is None) == (idx_host is None)
+        null = C.c_void_p(None)
+        if idx is None:
+            pi, ph = null, null
+        else:
+            ih = np.ascontiguousarray(idx_host, dtype=np.int32)
+            assert idx.dtype == torch.int32 and idx.numel() == n == ih.size
+            pi, ph = _p(idx), C.c_void_p(ih.ctypes.data)
+        check(self.lib.xmc_gather_rows_ln(_p(x), pi, ph, _p(gamma), _p(beta), _p(out), n, t, h, float(eps), self._stream()),
+              "xmc_gather_rows_ln")
+        return out
+
+    def _f32_rows(self, a):
+        if not isinstance(a, torch.Tensor):
+            a = torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32))
+        a = a.to(self.device) if a.device != self.device else a
+        assert a.dtype == torch.float32 and a.dim() == 2
+        return a.contiguous()
+
+    def pair_cosine(self, a, b, out=None):
+        """(n,) float64 ndarray: the cosine of row i of ``a`` and row i of ``b`` (``xmc_pair_cosine``; specification:
+        ``alignment_metrics.pair_cosine_spec``).  ``out``: a float64 device tensor to fill and return instead."""
+        a, b = self._f32_rows(a), self._f32_rows(b)
+        n, d = a.shape
+        assert b.shape == (n, d)
+        cos = torch.empty((n,), dtype=torch.float64, device=self.device) if out is None else out
+        assert cos.dtype == torch.float64 and cos.numel() >= n and cos.is_contiguous()
+        check(self.lib.xmc_pair_cosine(_p(a), _p(b), _p(cos), n, d, self._stream()), "xmc_pair_cosine")
+        return cos.cpu().numpy() if out is None else out
+
+    def rprecision_hits(self, img, txt, truth, cand, out=None):
+        """(n,) bool ndarray: is the cosine of image i with caption ``truth[i]`` strictly above its cosine with every caption
+        ``cand[i, j]`` (``xmc_rprecision_hits``).  ``truth`` (n,) / ``cand`` (n, c): integer HOST arrays, validated by the library
+        against the rows of ``txt`` before the launch.  ``out``: a uint8 device tensor to fill and return instead."""
+        img, txt = self._f32_rows(img), self._f32_rows(txt)
+        (n, d), m = img.shape, txt.shape[0]
+        th, ch = np.ascontiguousarray(truth, dtype=np.int32), np.ascontiguousarray(cand, dtype=np.int32)
+        assert txt.shape[1] == d and th.shape == (n,) and ch.ndim == 2 and ch.shape[0] == n
+        dt, dc = torch.from_numpy(th).to(self.device), torch.from_numpy(ch).to(self.device)
+        hit = torch.empty((n,), dtype=torch.uint8, device=self.device) if out is None else out
+        assert hit.dtype == torch.uint8 and hit.numel() >= n and hit.is_contiguous()
+        check(self.lib.xmc_rprecision_hits(_p(img), _p(txt), _p(dt), C.c_void_p(th.ctypes.data), _p(dc), C.c_void_p(ch.ctypes.data),
+                                           _p(hit), n, m, d, ch.shape[1], self._stream()), "xmc_rprecision_hits")
+        return hit.cpu().numpy().astype(bool) if out is None else out
+
     def probe_layouts(self):
         out = self.zeros((2 * 64 * 16 + 64 * 4,))
         check(_lib.load_probe().xmc_probe_layouts(_p(out), self._stream()), "xmc_probe_layouts")      # libxmc_probe.so: diagnostics

@@ -644,14 +644,16 @@ def train(config, workdir, test_mode=False, *, datasets=None):
     return state
 
 
-def test(config, workdir, *, datasets=None, inception_ckpt_path=None, inception=None, timeout=24 * 3600, task_manager_kw=None):
+def test(config, workdir, *, datasets=None, inception_ckpt_path=None, inception=None, timeout=24 * 3600, task_manager_kw=None,
+         clip=None):
     """The evaluation loop (reference train_utils.py:464-514): FID and Inception Score, from the current and from the EMA
     parameters, of every checkpoint of ``workdir/checkpoints-0`` that has no row in its ``scores.csv`` yet; waits for new
     checkpoints until ``timeout`` seconds pass without one or ``TRAIN_DONE`` appears.  The eight values go as ``eval/<name>`` to
-    ``scores.csv`` and to ``workdir/metrics.jsonl``; with ``config.eval_extra_metrics`` (``"kid"``, ``"precision_recall"``) so do the
+    ``scores.csv`` and to ``workdir/metrics.jsonl``; with ``config.eval_extra_metrics`` (``"kid"``, ``"precision_recall"``, ``"clip"``) so do the
     values ``EvalMetric.calculate_metrics`` adds.  A ``scores.csv`` that was started with another set of columns raises ValueError
     before anything is evaluated.  ``inception`` / ``inception_ckpt_path``: see ``EvalMetric`` (which is built
-    when the first checkpoint is found).  Returns the number of checkpoints evaluated."""
+    when the first checkpoint is found); ``clip``: its injected CLIP scorer (``"clip"`` only).  Returns the number of checkpoints
+    evaluated."""
     import os
     import torch.distributed as dist
     from .utils import checkpoint, eval_metrics, task_manager
@@ -677,7 +679,7 @@ def test(config, workdir, *, datasets=None, inception_ckpt_path=None, inception=
         if eval_metric is None:
             eval_metric = eval_metrics.EvalMetric(eval_iter, config, inception_ckpt_path=inception_ckpt_path, inception=inception,
                                                   chunk=int(config.get("eval_chunk", 256)),
-                                                  group=dist.group.WORLD if distributed else None)
+                                                  group=dist.group.WORLD if distributed else None, clip=clip)
         state = checkpoint.restore(path, state)
         if extras:
             values = eval_metric.calculate_metrics(generator, state, streams["eval"])
