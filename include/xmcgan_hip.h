@@ -38,7 +38,7 @@ extern "C" {
 #define XMC_F32 0
 #define XMC_BF16 1
 
-#define XMC_ABI_VERSION 34
+#define XMC_ABI_VERSION 35
 int xmc_abi_version(void);
 
 /* Launch-heuristic knobs -- split-K workgroup targets and tile-selection thresholds whose defaults were A/B'd inside the
@@ -981,6 +981,45 @@ int xmc_gather_rows_ln(const float* x, const int32_t* idx, const int32_t* idx_ho
 int xmc_pair_cosine(const float* a, const float* b, double* cos, int32_t n, int32_t d, void* stream);
 int xmc_rprecision_hits(const float* img, const float* txt, const int32_t* truth, const int32_t* truth_host, const int32_t* cand,
                         const int32_t* cand_host, uint8_t* hit, int32_t n, int32_t m, int32_t d, int32_t c, void* stream);
+
+/* ---- Data gradient of the CLIP image tower (config.clip_guidance_weight; utils/clip_utils.ClipEncoder.image_backward;
+ *      utils/clip_grad.py is the specification; csrc/clip_grad.hip, ABI 35) ----
+ * The adjoints of the kernels above that the pullback from an image embedding to the pixels crosses.  The weights are frozen:
+ * there is no weight gradient, and the dense adjoints dX = dY W run on xmc_gemm_f32 / xmc_gemm_f32_bf16mfma.  float32
+ * arithmetic (float64 inside the QuickGELU derivative, as in xmc_bias_quick_gelu), fixed xor trees across lanes, sums in
+ * ascending index order, no float atomics: two launches on the same inputs give the same bits.  Pointers are 16-byte aligned;
+ * XMC_EINVAL otherwise and for every size outside the stated domain (nothing is launched).
+ *
+ *  - xmc_mha_attention_bwd: qkv, bias_qkv, len, len_host, n, t, h, causal as xmc_mha_attention; dctx (n * t, h) -> dqkv
+ *    (n * t, 3 h), every element written, dqkv != qkv.  The probabilities P are recomputed from qkv with the forward kernel's
+ *    arithmetic; dP = dctx V^T, dS = P o (dP - rowsum(P o dP)) / 8, dQ = dS K, dK = dS^T Q, dV = P^T dctx.  Masked keys
+ *    contribute exactly 0.  One 256-thread workgroup per (sequence, head); k and v rows, 32 query rows of q and dctx and their
+ *    P and dS rows in LDS (120,064 bytes at t = 128).  Domain: 1 <= len[i] <= t <= 128, h % 64 == 0.
+ *  - xmc_ln_bwd_add: with y = LayerNorm(x) * gamma + beta and g = dy gamma: dx = rstd (g - mean(g) - xhat mean(g xhat)) + dres,
+ *    mean and biased variance of the row in two passes as the forward kernels.  dres may be NULL or alias dx; dx aliases neither
+ *    x nor dy.  h % 4 == 0, h <= 1024.  mode selects the forward kernel's row map:
+ *      XMC_LN_BWD_ROWS   (xmc_bias_add_ln)     x, dy, dres, dx (rows, h); pos NULL, t = 1.
+ *      XMC_LN_BWD_GATHER (xmc_gather_rows_ln on row 0) x, dres, dx (rows = n t, h), dy (n, h): row i t of dx takes the gradient
+ *                        of pooled row i, every other row 0 (+ dres); pos NULL.
+ *      XMC_LN_BWD_VISION (xmc_clip_vision_embed) x = the patch products (rows = n (t - 1), h), pos (t, h), dy (n t, h) -> dx
+ *                        (rows, h): row (i, j - 1) = LN-backward(x[i, j - 1] + pos[j], dy[i t + j]); the class row's gradient
+ *                        is dropped.  dres NULL, t >= 2.
+ *  - xmc_bias_quick_gelu_bwd: dv = dy (s + 1.702 v s (1 - s)), v = x + bias[column], s = 1 / (1 + exp(-1.702 v)); x is the
+ *    product WITHOUT its bias (what xmc_bias_quick_gelu read).  x, dy, dv (rows, f), f % 4 == 0; dv may be dy, never x.
+ *  - xmc_clip_preprocess_bwd: the exact transpose of xmc_clip_preprocess: dpatches (n (s / p)^2, 3 p p) -> dimages
+ *    (n, hw, hw, 3) float32 or bf16 (dtype), dX_c = Ry^T dY_c Rx / std3[c] with the same float32 taps.  Gather form: every
+ *    input pixel adds the output pixels whose window holds it, in ascending order, first along y, then along x.  One workgroup
+ *    per (image, input row).  Domain as xmc_clip_preprocess. */
+#define XMC_LN_BWD_ROWS 0
+#define XMC_LN_BWD_GATHER 1
+#define XMC_LN_BWD_VISION 2
+int xmc_mha_attention_bwd(const float* qkv, const float* bias_qkv, const int32_t* len, const int32_t* len_host, const float* dctx,
+                          float* dqkv, int32_t n, int32_t t, int32_t h, int32_t causal, void* stream);
+int xmc_ln_bwd_add(const float* x, const float* pos, const float* gamma, const float* dy, const float* dres, float* dx, int32_t rows,
+                   int32_t t, int32_t h, float eps, int32_t mode, void* stream);
+int xmc_bias_quick_gelu_bwd(const float* x, const float* bias, const float* dy, float* dv, int32_t rows, int32_t f, void* stream);
+int xmc_clip_preprocess_bwd(const float* dpatches, void* dimages, int32_t n, int32_t hw, int32_t s, int32_t p, const float* std3,
+                            int32_t dtype, void* stream);
 
 #ifdef __cplusplus
 }

@@ -18,7 +18,7 @@ LIB_PATH = os.path.join(_HERE, "libxmcgan_hip.so")
 PROBE_LIB_PATH = os.path.join(_HERE, "libxmc_probe.so")
 
 XMC_F32, XMC_BF16 = 0, 1
-ABI_VERSION = 34
+ABI_VERSION = 35
 
 # xmc_conv_desc.w_packed and xmc_wgrad_desc.variant: the names of include/xmcgan_hip.h (tests/test_conv_geometry.py keeps them equal)
 XMC_CONV_PACKED, XMC_CONV_PHASE, XMC_CONV_PHASE_PER_WG, XMC_CONV_COMPACT, XMC_CONV_NO_PX128 = 0x1, 0x10, 0x20, 0x40, 0x80
@@ -71,6 +71,7 @@ class TrainStatsArgs(C.Structure):   # mirrors xmc_train_stats_args
                [("d_grad_scale", C.c_float), ("g_grad_scale", C.c_float)]
 
 
+XMC_LN_BWD_ROWS, XMC_LN_BWD_GATHER, XMC_LN_BWD_VISION = 0, 1, 2
 TRAIN_STATS_N = 25                   # XMC_TRAIN_STATS_N
 CACHE_PLAN_STRIDE = 8                 # XMC_CACHE_PLAN_STRIDE
 
@@ -205,6 +206,10 @@ SIGNATURES = {
     "xmc_gather_rows_ln": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _F, _P],
     "xmc_pair_cosine": [_P, _P, _P, _I, _I, _P],
     "xmc_rprecision_hits": [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P],
+    "xmc_mha_attention_bwd": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P],
+    "xmc_ln_bwd_add": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _F, _I, _P],
+    "xmc_bias_quick_gelu_bwd": [_P, _P, _P, _P, _I, _I, _P],
+    "xmc_clip_preprocess_bwd": [_P, _P, _I, _I, _I, _I, _P, _I, _P],
     "xmc_metrics_accum": [_P, _I, _P, _P, _P],
     "xmc_segment_sumsq_ws_bytes": [_P, _I],
     "xmc_segment_sumsq": [_P, _L, _P, _P, _I, _P, _P, _P, _L, _P],

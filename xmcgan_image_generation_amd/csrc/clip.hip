@@ -18,6 +18,7 @@
 // inside QuickGELU), every cross-lane reduction a fixed xor tree, no atomics: two launches on the same inputs give the same bits,
 // and no sequence's result depends on what shares its launch.
 #include "common.h"
+#include "clip_taps.h"
 
 namespace {
 
@@ -218,35 +219,6 @@ __global__ __launch_bounds__(256) void mha_attention_kernel(const float* __restr
 }
 
 // ------------------------------------------------------------------------------------------------------------ preprocessing
-// Pillow's resampling coefficients (ImagingResample's precompute_coeffs with the bicubic filter, a = -0.5) for output index `o` of
-// an `in` -> `out` resize: the window starts at *lo and holds the returned number of taps (<= ksize); w[k] = the normalised
-// weights, computed in double as Pillow does and rounded to float32 once.
-__device__ __forceinline__ double keys_cubic(double x) {
-    x = fabs(x);
-    if (x < 1.0) return (1.5 * x - 2.5) * x * x + 1.0;               // ((a + 2) x - (a + 3)) x^2 + 1
-    if (x < 2.0) return (((x - 5.0) * x + 8.0) * x - 4.0) * -0.5;    // a (x^3 - 5 x^2 + 8 x - 4)
-    return 0.0;
-}
-
-__device__ __forceinline__ int cubic_taps(int o, int in, int out, int ksize, float* w, int* lo) {
-    const double scale = (double)in / (double)out;
-    const double fscale = scale < 1.0 ? 1.0 : scale;
-    const double support = 2.0 * fscale, ss = 1.0 / fscale;
-    const double center = (o + 0.5) * scale;
-    int xmin = (int)(center - support + 0.5);
-    if (xmin < 0) xmin = 0;
-    int xmax = (int)(center + support + 0.5);
-    if (xmax > in) xmax = in;
-    int cnt = xmax - xmin;
-    if (cnt > ksize) cnt = ksize;                                    // (never: ksize = 2 ceil(support) + 1; keeps the table's bounds local)
-    double ww = 0.0;
-    for (int k = 0; k < cnt; ++k) ww += keys_cubic((k + xmin - center + 0.5) * ss);
-    const double inv = ww != 0.0 ? 1.0 / ww : 0.0;
-    for (int k = 0; k < cnt; ++k) w[k] = (float)(keys_cubic((k + xmin - center + 0.5) * ss) * inv);
-    *lo = xmin;
-    return cnt;
-}
-
 template <typename T> __device__ __forceinline__ float px(const T* p, size_t i);
 template <> __device__ __forceinline__ float px<float>(const float* p, size_t i) { return p[i]; }
 template <> __device__ __forceinline__ float px<bf16_t>(const bf16_t* p, size_t i) { return bf2f(p[i]); }

@@ -398,6 +398,15 @@ def create_datasets(config, data_rng: int = 0, rank: int = 0, world: int = 1, de
                               data_dir=config.get("data_dir", "data/"), coco_version=config.get("coco_version", "2014"),
                               return_text=config.get("return_text", False), return_filename=config.get("return_filename", False),
                               return_caption_text=True)
+    # config.clip_guidance_weight > 0: train() embeds the text of the caption each TRAINING example drew, too (same switch of the
+    # dataset: the draw itself is unchanged, a record without that text raises ValueError)
+    guided = float(config.get("clip_guidance_weight", 0.0) or 0.0) > 0.0
+    ds_train = ds_eval if (guided and caption_text) else ds
+    if guided and not caption_text:
+        ds_train = COCODataset(image_size=config.image_size, z_dim=config.z_dim, data_dtype=dtype,
+                               data_dir=config.get("data_dir", "data/"), coco_version=config.get("coco_version", "2014"),
+                               return_text=config.get("return_text", False), return_filename=config.get("return_filename", False),
+                               return_caption_text=True)
     seed = int(data_rng)
     if workers is None:
         workers = int(config.get("num_decode_workers", 4))
@@ -434,10 +443,10 @@ def create_datasets(config, data_rng: int = 0, rank: int = 0, world: int = 1, de
             import logging
             logging.getLogger(__name__).warning("num_decode_procs=%d resolved to %d decode processes x %d thread(s) on this host: the "
                                                 "training-data order of a seed depends on that count", requested, procs, workers)
-        train = _batches_mp(ds_kw, shard("train"), [seed, 0, rank], config.get("train_shuffle", True), sb, True, True,
-                            per_device_train, procs, max(1, workers))
+        train = _batches_mp(dict(ds_kw, return_caption_text=True) if guided else ds_kw, shard("train"), [seed, 0, rank],
+                            config.get("train_shuffle", True), sb, True, True, per_device_train, procs, max(1, workers))
     else:
-        train = _batches(_examples(ds, shard("train"), [seed, 0, rank], config.get("train_shuffle", True), sb, True, True,
+        train = _batches(_examples(ds_train, shard("train"), [seed, 0, rank], config.get("train_shuffle", True), sb, True, True,
                                    workers), per_device_train)
     evalb = _batches(_examples(ds_eval, shard("val"), [seed, 1, rank], True, sb, True, False, workers),
                      max(1, config.get("eval_batch_size", per_device) // world))

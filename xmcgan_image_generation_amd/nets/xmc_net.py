@@ -93,6 +93,17 @@ def check_config(config):
     if config.get("conv_fp8_phase_in", False) and not config.get("conv_fp8", False):
         raise ValueError("conv_fp8_phase_in=True needs conv_fp8=True: it moves the in-form phase launches of the MX-fp8 mode "
                          "onto the MX-fp8 \"in\" phase kernel and means nothing in the bf16 mode")
+    lam = float(config.get("clip_guidance_weight", 0.0) or 0.0)
+    if lam < 0.0 or lam != lam:
+        raise ValueError(f"clip_guidance_weight={config.get('clip_guidance_weight')} must be >= 0: it weighs a loss term the "
+                         "generator minimises (0 = off)")
+    if lam > 0.0:
+        if not config.get("clip_vocab_path", None) or not config.get("clip_merges_path", None):
+            raise ValueError("clip_guidance_weight > 0 needs clip_vocab_path and clip_merges_path (CLIP's vocab.json and merges.txt; "
+                             "INTEGRATION.md): the captions are tokenised for the frozen text tower, and nothing is downloaded")
+        if config.get("device_dataset_cache", False):
+            raise ValueError("clip_guidance_weight > 0 is not supported with device_dataset_cache=True: the cache carries no caption "
+                             "strings, and the term embeds each training caption's text; train with device_dataset_cache=False")
     extras = tuple(config.get("eval_extra_metrics", ()))
     if extras:
         from ..utils.eval_metrics import extra_metric_keys

@@ -1902,6 +1902,70 @@ class HipOps:
               "xmc_gather_rows_ln")
         return out
 
+    # ------------------------------------- data gradient of the CLIP image tower (utils/clip_utils.ClipEncoder.image_backward;
+    # specification: utils/clip_grad.py)
+    def mha_attention_bwd(self, qkv, bias_qkv, lens, lens_host, dctx, t, causal=False, out=None):
+        """dqkv (n * t, 3 h) <- the pullback of ``mha_attention`` at ``dctx`` (n * t, h); the probabilities are recomputed from
+        ``qkv`` (the product WITHOUT its bias, as the forward read it)"""
+        rows, h3 = qkv.shape
+        n, h = rows // t, h3 // 3
+        lh = np.ascontiguousarray(lens_host, dtype=np.int32)
+        out = self.empty((rows, h3), torch.float32) if out is None else out
+        assert rows == n * t and h3 == 3 * h and dctx.shape == (rows, h) and out.shape == (rows, h3)
+        assert qkv.is_contiguous() and dctx.is_contiguous() and out.is_contiguous()
+        assert qkv.dtype == dctx.dtype == out.dtype == torch.float32 and lens.dtype == torch.int32 and lens.numel() == n == lh.size
+        assert bias_qkv.numel() == h3
+        check(self.lib.xmc_mha_attention_bwd(_p(qkv), _p(bias_qkv), _p(lens), C.c_void_p(lh.ctypes.data), _p(dctx), _p(out), n, t, h,
+                                             int(bool(causal)), self._stream()), "xmc_mha_attention_bwd")
+        return out
+
+    def ln_bwd_add(self, x, gamma, dy, dres=None, out=None, eps=1e-5, mode="rows", t=1, pos=None):
+        """out <- LN-backward(x, gamma, dy) (+ ``dres``, which may be ``out``), float32 rows of h.  ``mode``: "rows" (x, dy, out
+        (rows, h)); "gather" (x, out (n * t, h), dy (n, h): row 0 of every sequence takes the pooled row's gradient, the others
+        0 (+ dres)); "vision" (x = the patch products (n * (t - 1), h), ``pos`` (t, h), dy (n * t, h) -> out (n * (t - 1), h):
+        the pullback of ``clip_vision_embed`` to the patch rows)"""
+        code = {"rows": _lib.XMC_LN_BWD_ROWS, "gather": _lib.XMC_LN_BWD_GATHER, "vision": _lib.XMC_LN_BWD_VISION}[mode]
+        rows, h = x.shape
+        out = self.empty((rows, h), torch.float32) if out is None else out
+        if mode == "rows":
+            assert dy.shape == (rows, h) and pos is None and t == 1
+        elif mode == "gather":
+            assert rows % t == 0 and dy.shape == (rows // t, h) and pos is None
+        else:
+            assert t >= 2 and rows % (t - 1) == 0 and dy.shape == (rows // (t - 1) * t, h) and pos.shape == (t, h) and dres is None
+            assert pos.dtype == torch.float32 and pos.is_contiguous()
+        for t_ in (x, dy, dres, out):
+            assert t_ is None or (t_.dtype == torch.float32 and t_.is_contiguous())
+        assert out.shape == (rows, h) and (dres is None or dres.shape == (rows, h)) and gamma.numel() == h
+        null = C.c_void_p(None)
+        check(self.lib.xmc_ln_bwd_add(_p(x), null if pos is None else _p(pos), _p(gamma), _p(dy), null if dres is None else _p(dres),
+                                      _p(out), rows, int(t), h, float(eps), code, self._stream()), "xmc_ln_bwd_add")
+        return out
+
+    def bias_quick_gelu_bwd(self, x, bias, dy, out=None):
+        """dy * d/dv [v sigmoid(1.702 v)] at v = x + bias, (rows, f) float32; ``out`` may be ``dy``"""
+        rows, f = x.shape
+        out = self.empty(x.shape, torch.float32) if out is None else out
+        assert x.dtype == dy.dtype == out.dtype == torch.float32 and dy.shape == out.shape == x.shape
+        assert x.is_contiguous() and dy.is_contiguous() and out.is_contiguous() and bias.numel() == f
+        check(self.lib.xmc_bias_quick_gelu_bwd(_p(x), _p(bias), _p(dy), _p(out), rows, f, self._stream()), "xmc_bias_quick_gelu_bwd")
+        return out
+
+    def clip_preprocess_bwd(self, dpatches, hw, size, patch, std, dtype=torch.float32, out=None):
+        """(n * (size / patch)^2, 3 * patch^2) float32 -> (n, hw, hw, 3) ``dtype`` (float32 / bf16): the transpose of
+        ``clip_preprocess`` (``xmc_clip_preprocess_bwd``; specification: ``clip_grad.preprocess_adjoint``)"""
+        g = size // patch
+        rows, cols = dpatches.shape
+        n = rows // (g * g)
+        assert rows == n * g * g and cols == 3 * patch * patch and dpatches.dtype == torch.float32 and dpatches.is_contiguous()
+        out = self.empty((n, hw, hw, 3), dtype) if out is None else out
+        assert out.shape == (n, hw, hw, 3) and out.dtype in (torch.float32, torch.bfloat16) and out.is_contiguous()
+        s3 = np.ascontiguousarray(std, dtype=np.float32)
+        assert s3.shape == (3,)
+        check(self.lib.xmc_clip_preprocess_bwd(_p(dpatches), _p(out), n, int(hw), int(size), int(patch), C.c_void_p(s3.ctypes.data),
+                                               _code(out.dtype), self._stream()), "xmc_clip_preprocess_bwd")
+        return out
+
     def _f32_rows(self, a):
         if not isinstance(a, torch.Tensor):
             a = torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32))

@@ -581,16 +581,26 @@ def train(config, workdir, test_mode=False, *, datasets=None):
         with open(os.path.join(workdir, "config.json"), "w") as f:
             json.dump(dict(config), f, indent=1, sort_keys=True, default=str)
     use_graph = ops.device.type == "cuda" and xmc_net._OPS_FACTORY is None
-    accumulator = MetricAccumulator(xmc_gan.METRIC_KEYS, ops)
+    accumulator = MetricAccumulator(xmc_gan.metric_keys(config), ops)
     writer = JsonlWriter(os.path.join(workdir, "metrics.jsonl"))
     statistics = additional_data.get("statistics")   # config.train_statistics: filled by train_g_d, read at the boundaries below
     graphed, window_start = None, initial_step
     n_split = config.d_step_per_g_step
     from .libml import diff_augment
     aug_policy = config.get("diff_augment", "")      # differentiable augmentation of D's inputs: a plan per step, like z
+    clip_guidance = additional_data.get("clip_guidance") if gan_model is xmc_gan else None      # config.clip_guidance_weight > 0
     for step in range(initial_step, num_train_steps + 1):
         is_last_step = step == num_train_steps
-        batch = {k: v.to(ops.device) for k, v in _array_fields(next(train_iter)).items()}
+        item = next(train_iter)
+        batch = {k: v.to(ops.device) for k, v in _array_fields(item).items()}
+        if clip_guidance is not None:
+            # the frozen CLIP text tower on this step's captions: eagerly, on the step's stream, BETWEEN graph launches (the
+            # token ids are validated on the host) -- a device tensor that load_batch copies into the graph's static batch
+            from .utils.eval_metrics import _captions
+            if "text" not in item:
+                raise ValueError('clip_guidance_weight > 0 needs the captions\' text in every training batch (batch["text"]: '
+                                 "COCODataset(return_caption_text=True), which create_datasets sets on the training stream)")
+            batch["clip_text"] = clip_guidance.embed_text(ops, _captions(item))
         if aug_policy:
             # a pure function of (seed, step, rank): a resumed run draws what the uninterrupted one did.  Left on the host -- the
             # eager step validates it there, GraphedTrainStep.load_batch copies it into the graph's static tensor

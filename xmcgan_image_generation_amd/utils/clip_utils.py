@@ -3,7 +3,10 @@ embeddings out -- what the alignment metrics of ``utils/alignment_metrics.py`` a
 
 ``clip_model`` reads the weights: an ``.npz`` whose keys are the state-dict names of a Hugging Face ``CLIPModel`` (one
 ``np.savez(path, **{k: v.numpy() for k, v in model.state_dict().items()})``; INTEGRATION.md).  Nothing is downloaded.
-``ClipEncoder`` is the network; ``ClipScorer`` the public interface (tokenizer + network).
+``ClipEncoder`` is the network; ``ClipScorer`` the public interface (tokenizer + network) of the metrics.  ``ClipGuidance`` is what
+``train_g_d`` trains against with ``config.clip_guidance_weight``: the image tower with a tape (``image_device(images,
+tape=True)``) and its data gradient (``image_backward``; ``csrc/clip_grad.hip``, specification ``utils/clip_grad.py``), and the
+text side that ``train()`` runs outside the captured step.
 """
 from __future__ import annotations
 
@@ -160,29 +163,57 @@ class ClipEncoder:
         self.launches += 1
         return self.ops.gemm(x, w, tb=True, out=out, fast=self.fast, split_k=False)
 
-    def _blocks(self, b, layers, t, causal, final):
+    def _blocks(self, b, layers, t, causal, final, tape=None):
         """the residual stream b["h"] through ``layers``; returns it.  The last add also normalises with ``final`` (unused rows:
-        the pooled row is normalised again from the stream by the caller's gather)"""
-        ops, h, y = self.ops, b["h"], b["y"]
+        the pooled row is normalised again from the stream by the caller's gather).  ``tape`` (``tape_buffers``): the same launches
+        in the same order, but every state of the stream, every ``qkv`` and every pre-activation ``ff`` goes to a buffer of its own
+        (the stream is then ``tape["hs"][0]`` on entry and ``tape["hs"][-1]`` on return)"""
+        ops, y = self.ops, b["y"]
+        h = b["h"] if tape is None else tape["hs"][0]
         n = b["len"].numel()
         lens_host = np.full((n,), t, np.int32)
         ops.bias_add_ln(h, None, None, layers[0]["w_ln1"], layers[0]["b_ln1"], out=y, eps=arch.LN_EPS)
         self.launches += 1
         for i, L in enumerate(layers):
-            self._gemm(y, L["w_qkv"], b["qkv"])
-            ops.mha_attention(b["qkv"], L["b_qkv"], b["len"], lens_host, b["ctx"], t, causal=causal)
+            qkv, ff = (b["qkv"], b["ff"]) if tape is None else (tape["qkv"][i], tape["ff"][i])
+            mid, nxt = (h, h) if tape is None else (tape["hs"][2 * i + 1], tape["hs"][2 * i + 2])
+            self._gemm(y, L["w_qkv"], qkv)
+            ops.mha_attention(qkv, L["b_qkv"], b["len"], lens_host, b["ctx"], t, causal=causal)
             self._gemm(b["ctx"], L["w_o"], b["prod"])
-            ops.bias_add_ln(b["prod"], L["b_o"], h, L["w_ln2"], L["b_ln2"], s=h, out=y, eps=arch.LN_EPS)
-            self._gemm(y, L["w_fc1"], b["ff"])
-            ops.bias_quick_gelu(b["ff"], L["b_fc1"], out=b["ff"])
+            ops.bias_add_ln(b["prod"], L["b_o"], h, L["w_ln2"], L["b_ln2"], s=mid, out=y, eps=arch.LN_EPS)
+            self._gemm(y, L["w_fc1"], ff)
+            ops.bias_quick_gelu(ff, L["b_fc1"], out=b["ff"])
             self._gemm(b["ff"], L["w_fc2"], b["prod"])
             g, be = (layers[i + 1]["w_ln1"], layers[i + 1]["b_ln1"]) if i + 1 < len(layers) else final
-            ops.bias_add_ln(b["prod"], L["b_fc2"], h, g, be, s=h, out=y, eps=arch.LN_EPS)
+            ops.bias_add_ln(b["prod"], L["b_fc2"], mid, g, be, s=nxt, out=y, eps=arch.LN_EPS)
+            h = nxt
             self.launches += 4
         return h
 
-    def image_device(self, images):
-        """one chunk -> (n, proj) float32 device tensor owned by this object, valid until the next call of the same shape"""
+    def tape_buffers(self, n):
+        """what ``image_backward`` reads, for a chunk of n images: the stream entering each LayerNorm (2 L + 1 states), each
+        layer's ``qkv`` and pre-activation ``ff``, the patch products, and the pullback's own scratch.  One set per n, reused from call to call as the
+        ResNet-50 tape's buffers are: a tape is valid until the next taped call of the same n (77 MB per layer at ViT-B/32 and
+        n = 56, 0.9 GB in all)."""
+        key = ("tape", n)
+        tb = self._bufs.get(key)
+        if tb is None:
+            ops, d, f32 = self.ops, self.dims, torch.float32
+            rows, h, f, L = n * d.vision_tokens, d.vision_width, d.vision_ffn, d.vision_layers
+            prow = n * (d.vision_tokens - 1)
+            tb = {"hs": [ops.empty((rows, h), f32) for _ in range(2 * L + 1)],
+                  "qkv": [ops.empty((rows, 3 * h), f32) for _ in range(L)], "ff": [ops.empty((rows, f), f32) for _ in range(L)],
+                  "dh": ops.empty((rows, h), f32), "dy": ops.empty((rows, h), f32), "dqkv": ops.empty((rows, 3 * h), f32),
+                  "dff": ops.empty((rows, f), f32), "dpooled": ops.empty((n, h), f32), "dpe": ops.empty((prow, h), f32),
+                  "pe": ops.empty((prow, h), f32),
+                  "dpatches": ops.empty((prow, 3 * d.patch * d.patch), f32)}
+            self._bufs[key] = tb
+        return tb
+
+    def image_device(self, images, tape=False):
+        """one chunk -> (n, proj) float32 device tensor owned by this object, valid until the next call of the same shape.
+        ``tape=True`` -> (emb, tape): the same kernels in the same order (``emb`` has the same bits), with what
+        ``image_backward`` needs kept in ``tape_buffers(n)``"""
         d, ops = self.dims, self.ops
         if not isinstance(images, torch.Tensor):
             images = torch.from_numpy(np.ascontiguousarray(images, dtype=np.float32))
@@ -195,14 +226,81 @@ class ClipEncoder:
         images = images.to(ops.device).contiguous()
         n, t, v = images.shape[0], d.vision_tokens, self.vision
         b = self.buffers("vision", n, t, d.vision_width, d.vision_ffn)
+        rec = None
+        if tape:
+            rec = dict(self.tape_buffers(n), n=n, hw=images.shape[1], dtype=images.dtype, len=b["len"])
         ops.clip_preprocess(images, d.image_size, d.patch, arch.IMAGE_MEAN, arch.IMAGE_STD, out=b["patches"])
-        self._gemm(b["patches"], v["w_patch"], b["pe"])
-        ops.clip_vision_embed(b["pe"], v["cls"], v["pos"], *v["pre"], b["h"], t, eps=arch.LN_EPS)
+        pe = b["pe"] if rec is None else rec["pe"]
+        self._gemm(b["patches"], v["w_patch"], pe)
+        ops.clip_vision_embed(pe, v["cls"], v["pos"], *v["pre"], b["h"] if rec is None else rec["hs"][0], t, eps=arch.LN_EPS)
         self.launches += 2
-        h = self._blocks(b, v["layers"], t, False, v["final"])
+        h = self._blocks(b, v["layers"], t, False, v["final"], rec)
         ops.gather_rows_ln(h, None, None, *v["final"], t, out=b["pooled"], eps=arch.LN_EPS)
         self.launches += 1
-        return self._gemm(b["pooled"], v["w_proj"], b["emb"])
+        emb = self._gemm(b["pooled"], v["w_proj"], b["emb"])
+        return emb if rec is None else (emb, rec)
+
+    def _dgemm(self, dy, w, out, alpha=1.0):
+        """the dense adjoint dX = alpha dY W on the (out, in) weight: the forward's GEMM entry point, operands rounded as there"""
+        self.launches += 1
+        return self.ops.gemm(dy, w, alpha=alpha, out=out, fast=self.fast, split_k=False)
+
+    def _grad_op(self, name):
+        """a kernel of csrc/clip_grad.hip, or its float64 specification on an operator table without it"""
+        fn = getattr(self.ops, name, None)
+        if fn is not None:
+            return fn
+        from . import clip_grad
+        spec = {"mha_attention_bwd": lambda qkv, bias, lens, lens_host, dctx, t, causal=False, out=None:
+                clip_grad.attention_bwd(qkv.cpu(), bias.cpu(), lens_host, dctx.cpu(), t, causal),
+                "ln_bwd_add": lambda x, gamma, dy, dres=None, out=None, eps=1e-5, mode="rows", t=1, pos=None:
+                clip_grad.ln_bwd_add(x.cpu(), gamma.cpu(), dy.cpu(), None if dres is None else dres.cpu(), eps, mode, t,
+                                     None if pos is None else pos.cpu()),
+                "bias_quick_gelu_bwd": lambda x, bias, dy, out=None: clip_grad.bias_quick_gelu_bwd(x.cpu(), bias.cpu(), dy.cpu()),
+                "clip_preprocess_bwd": lambda dp, hw, size, patch, std, dtype=torch.float32, out=None:
+                clip_grad.preprocess_adjoint(dp.cpu(), hw, size, patch, std)}[name]
+
+        def run(*args, out=None, **kw):
+            res = torch.from_numpy(np.ascontiguousarray(spec(*args, **kw)))
+            if out is None:
+                return res.to(kw.get("dtype", torch.float32)).to(self.ops.device)
+            return out.copy_(res.to(out.dtype))
+        return run
+
+    def image_backward(self, tape, demb, dtype=None, scale=1.0):
+        """the pullback of ``image_device(images, tape=True)``: demb (n, proj) float32 -> d images (n, H, W, 3) in ``dtype``
+        (default: the images' own).  The weights are frozen: data gradient only.  Per block, backwards: GEMM (fc2), QuickGELU',
+        GEMM (fc1), LayerNorm' + residual, GEMM (out), attention', GEMM (q | k | v), LayerNorm' + residual; around them the
+        pooled row's LayerNorm' (scattered to the class rows), pre_layrnorm's (class row dropped), the patch GEMM and the
+        transpose of the preprocessing.  ``scale`` multiplies the result (a loss weight; folded into the first product).  The
+        result is a new tensor; everything else lives in the tape's buffers."""
+        d, ops, v = self.dims, self.ops, self.vision
+        n, t = tape["n"], d.vision_tokens
+        demb = demb.to(ops.device, torch.float32).contiguous()
+        if tuple(demb.shape) != (n, d.proj):
+            raise ValueError(f"demb must be ({n}, {d.proj}), got {tuple(demb.shape)}")
+        ln, attn, gelu, pre = (self._grad_op(k) for k in ("ln_bwd_add", "mha_attention_bwd", "bias_quick_gelu_bwd",
+                                                           "clip_preprocess_bwd"))
+        dh, dy, hs = tape["dh"], tape["dy"], tape["hs"]
+        lens_host = np.full((n,), t, np.int32)
+        self._dgemm(demb, v["w_proj"], tape["dpooled"], alpha=float(scale))
+        ln(hs[-1], v["final"][0], tape["dpooled"], out=dh, eps=arch.LN_EPS, mode="gather", t=t)
+        self.launches += 1
+        for i in reversed(range(d.vision_layers)):
+            L = v["layers"][i]
+            self._dgemm(dh, L["w_fc2"], tape["dff"])
+            gelu(tape["ff"][i], L["b_fc1"], tape["dff"], out=tape["dff"])
+            self._dgemm(tape["dff"], L["w_fc1"], dy)
+            ln(hs[2 * i + 1], L["w_ln2"], dy, dres=dh, out=dh, eps=arch.LN_EPS)
+            self._dgemm(dh, L["w_o"], dy)
+            attn(tape["qkv"][i], L["b_qkv"], tape["len"], lens_host, dy, t, causal=False, out=tape["dqkv"])
+            self._dgemm(tape["dqkv"], L["w_qkv"], dy)
+            ln(hs[2 * i], L["w_ln1"], dy, dres=dh, out=dh, eps=arch.LN_EPS)
+            self.launches += 4
+        ln(tape["pe"], v["pre"][0], dh, out=tape["dpe"], eps=arch.LN_EPS, mode="vision", t=t, pos=v["pos"])
+        self._dgemm(tape["dpe"], v["w_patch"], tape["dpatches"])
+        self.launches += 2
+        return pre(tape["dpatches"], tape["hw"], d.image_size, d.patch, arch.IMAGE_STD, dtype=dtype or tape["dtype"])
 
     def text_device(self, ids, eot):
         """one chunk -> (n, proj) float32 device tensor owned by this object"""
@@ -236,6 +334,48 @@ class ClipEncoder:
         out = np.empty((n, self.dims.proj), np.float32)
         for lo in range(0, n, self.chunk):
             out[lo:lo + self.chunk] = self.text_device(ids[lo:lo + self.chunk], eot[lo:lo + self.chunk]).cpu().numpy()
+        return out
+
+
+class ClipGuidance:
+    """What ``xmc_gan.create_additional_data`` hands to ``train_g_d`` as ``clip_guidance`` (config.clip_guidance_weight > 0): the
+    frozen CLIP's weights and tokenizer.  Like the ResNet-50's ``ImageModel`` it binds itself to the step's operator table on
+    first use (``bind``).  ``embed_text(ops, captions)`` is the text side, run OUTSIDE the step: strings -> (rows, proj) float32
+    device tensor, the batch's ``clip_text``.  ``keep`` (tests): the last half step's images, embeddings, text rows and image
+    cotangent are retained in ``kept``."""
+
+    def __init__(self, params, tokenizer, fast=False, chunk=256):
+        self.params, self.tokenizer, self.fast, self.chunk = params, tokenizer, bool(fast), max(1, int(chunk))
+        self.dims = validate(params)
+        self.proj = self.dims.proj
+        if tokenizer is not None and tokenizer.vocab_size > self.dims.vocab:
+            raise ValueError(f"the BPE vocabulary has {tokenizer.vocab_size} entries, the token table {self.dims.vocab} rows")
+        self.encoder, self.keep, self.kept = None, False, None
+
+    @classmethod
+    def from_config(cls, config):
+        path = config.get("clip_ckpt_path", None)
+        if path is None:
+            warnings.warn("clip_guidance_weight > 0 with random CLIP weights (clip_ckpt_path=None): the term then pulls the "
+                          "generator towards nothing meaningful; convert the real weights and pass their path", stacklevel=2)
+        fast = config.get("clip_guidance_fast", None)
+        fast = config.dtype == "bfloat16" if fast is None else bool(fast)
+        return cls(clip_model(path), clip_bpe.ClipTokenizer(config.clip_vocab_path, config.clip_merges_path), fast=fast)
+
+    def bind(self, ops):
+        if self.encoder is None or self.encoder.ops is not ops:
+            self.encoder = ClipEncoder(ops, self.params, fast=self.fast, chunk=self.chunk)
+        return self.encoder
+
+    def embed_text(self, ops, captions):
+        """the frozen text tower on the current stream, chunked as ``encode_text``; the WHOLE list is checked before anything runs"""
+        enc = self.bind(ops)
+        ids, eot = self.tokenizer.encode([c.decode("utf-8") if isinstance(c, bytes) else str(c) for c in captions], self.dims.context)
+        ids, eot = np.asarray(ids), np.asarray(eot)
+        check_text(ids, eot, self.dims.vocab, self.dims.context)
+        out = ops.empty((ids.shape[0], self.proj), torch.float32)
+        for lo in range(0, ids.shape[0], self.chunk):
+            out[lo:lo + self.chunk].copy_(enc.text_device(ids[lo:lo + self.chunk], eot[lo:lo + self.chunk]))
         return out
 
 

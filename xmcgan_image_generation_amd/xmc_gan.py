@@ -9,6 +9,9 @@ replaced by an explicit schedule over the HIP kernels:
     train_g_d : G fwd (tape)    -> D fwd -> D backward (d-stream) -> D backward (g-stream: fake
                 half only, dgrad only) -> G backward
 
+With ``config.clip_guidance_weight`` > 0 (not in the reference) train_g_d also runs the frozen CLIP image tower on the generated
+images and adds lambda times its pullback into their cotangent before the G backward (``_clip_loss``).
+
 ``lax.pmean`` (xmc_gan.py:170-171,251) becomes an RCCL all-reduce of the flat gradient arena
 (``dp.GradSync``), issued on a side HIP stream so that the discriminator's gradient exchange
 overlaps the g-stream / generator backward; the 1/world factor is folded into the Adam kernel.
@@ -63,6 +66,17 @@ def _ovl(ops, flag):
 
 
 METRIC_KEYS = ("d_loss", "g_loss", "c_loss_d", "c_loss_g", "c_loss_g_pretrained")
+CLIP_METRIC_KEY = "c_loss_g_clip"
+
+
+def clip_guidance_weight(config):
+    """lambda of the frozen-CLIP image-text term (``config.clip_guidance_weight``; absent or 0 = off)"""
+    return float(config.get("clip_guidance_weight", 0.0) or 0.0)
+
+
+def metric_keys(config):
+    """the keys of train_g_d's metrics under ``config``: ``METRIC_KEYS``, and ``c_loss_g_clip`` with the CLIP term on"""
+    return METRIC_KEYS + ((CLIP_METRIC_KEY,) if clip_guidance_weight(config) > 0.0 else ())
 
 
 def create_additional_data(config):
@@ -79,6 +93,10 @@ def create_additional_data(config):
     if config.get("train_statistics", False):        # build-side: in-graph statistics of train_g_d (train_statistics.py)
         from .train_statistics import TrainStatistics
         additional_data["statistics"] = TrainStatistics()
+    if clip_guidance_weight(config) > 0.0:           # (not in the reference) the frozen CLIP of the image-text term, built once
+        from .utils import clip_utils
+        xmc_net.check_config(config)                 # the two BPE paths are there; ValueError otherwise
+        additional_data["clip_guidance"] = clip_utils.ClipGuidance.from_config(config)
     return additional_data
 
 
@@ -148,6 +166,35 @@ def calculate_contrastive_loss_on_pretrained(model, state, real_images, fake_ima
     ops = ops if ops is not None else model.ops
     feats, outputs, rtape = _pretrained_forward(model, real_images, fake_images, ops)
     return _pretrained_loss(ops, feats, outputs, rtape, real_images.shape[0], loss_acc)
+
+
+def _clip_text_rows(ops, config, batch, b, guidance):
+    """``batch["clip_text"]`` of this half step: the frozen CLIP text tower's un-normalised embeddings of its captions, (b, proj)
+    float32 -- computed OUTSIDE the step (``train()`` does, eagerly, between graph launches; ``ClipGuidance.embed_text``)"""
+    if "clip_text" not in batch:
+        raise ValueError("config.clip_guidance_weight > 0 but the batch has no 'clip_text' (ClipGuidance.embed_text of the "
+                         "captions: float32 [rows, proj], split like 'sentence_embedding')")
+    text = torch.as_tensor(batch["clip_text"])
+    if tuple(text.shape) != (b, guidance.proj):
+        raise ValueError(f"batch['clip_text'] must be ({b}, {guidance.proj}), got {tuple(text.shape)}")
+    return xmc_net._to_dev(ops, text).to(torch.float32).contiguous()
+
+
+def _clip_loss(ops, config, guidance, cpre, loss_acc=None):
+    """contrastive_loss(E_img(img), clip_text) in both directions at the default temperature -> (loss (1,), pullback);
+    ``pullback()`` returns lambda * d loss / d img in the images' dtype (the text rows carry no gradient)"""
+    emb, tape, text, img = cpre
+    acc = loss_acc if loss_acc is not None else ops.zeros((1,))
+    ctape = attn_lib.contrastive_loss_fwd(ops, emb, text, acc)
+
+    def pullback():
+        demb, _ = attn_lib.contrastive_loss_bwd(ops, ctape, want_b=False)
+        dimg = guidance.encoder.image_backward(tape, demb, scale=clip_guidance_weight(config))
+        if guidance.keep:                            # (tests) what this half step read and produced
+            guidance.kept = dict(img=img.detach().clone(), emb=emb.detach().clone(), text=text.detach().clone(),
+                                 dimg=dimg.detach().clone(), loss=acc)
+        return dimg
+    return acc, pullback
 
 
 def _leaf_tensors(obj):
@@ -258,9 +305,11 @@ def _generator_forward(rng, config, state, batch, g, need_tape):
                      need_tape=need_tape)
 
 
-def _forward(rng, config, state, batch, g, d, need_g_tape, image_model=None, after_trunk=None, want_metrics=True, stats=None):
+def _forward(rng, config, state, batch, g, d, need_g_tape, image_model=None, after_trunk=None, want_metrics=True, stats=None,
+             clip=None):
     """``stats`` (a ``TrainStatistics``, train_g_d only): the discriminator forward also computes the heads' accuracy / entropy
-    pairs and hands its logits, losses and sigmas to it"""
+    pairs and hands its logits, losses and sigmas to it.  ``clip`` (a ``ClipGuidance``, train_g_d with config.clip_guidance_weight
+    only): the frozen CLIP image tower's forward on the generated images, with its tape"""
     ops = g.ops
     cond = {k: batch[k] for k in ("sentence_embedding", "embedding", "max_len")}
     deferred = getattr(state, "pending", None) is not None
@@ -309,6 +358,17 @@ def _forward(rng, config, state, batch, g, d, need_g_tape, image_model=None, aft
                 pre = _pretrained_forward(image_model, real, img, ops, batch["image"])
         else:
             pre = _pretrained_forward(image_model, real, img, ops, batch["image"])
+    cpre = None
+    if clip is not None:
+        # the frozen CLIP image tower reads the PLAIN generated images, as the ResNet-50 term does, and runs where that one runs:
+        # on the side stream (where its pullback will be issued or joined), beside the discriminator's forward below
+        text = _clip_text_rows(ops, config, batch, img.shape[0], clip)
+        enc = clip.bind(ops)
+        if _ovl(ops, _OVERLAP_BWD) and hasattr(ops, "side"):
+            with ops.side():
+                cpre = enc.image_device(img, tape=True) + (text, img)
+        else:
+            cpre = enc.image_device(img, tape=True) + (text, img)
     logit, loss_vec, new_sn, d_tape = d.forward(state.d_optimizer.target,
                                                 state.discriminator_state["spectral_norm_stats"], all_images,
                                                 cond, need_tape=True, fake_losses=need_g_tape, prepared=new_sn,
@@ -330,7 +390,7 @@ def _forward(rng, config, state, batch, g, d, need_g_tape, image_model=None, aft
         rd = {k: loss_vec[i] for i, k in enumerate(xmc_net.LOSS_SLOTS)}
         c_loss_d, c_loss_g = calculate_contrastive_loss(rd)
         out = dict(d_loss=hinge[0] + c_loss_d, g_loss=hinge[1] + c_loss_g, c_loss_d=c_loss_d, c_loss_g=c_loss_g)
-    return state, out, dld, dlg, g_tape, d_tape, new_g_stats, new_sn, pre
+    return state, out, dld, dlg, g_tape, d_tape, new_g_stats, new_sn, pre, cpre
 
 
 def _apply_adam(ops, opt, config, lr, grad_scale, ema=None, fix_args=None, net=None, stats=None):
@@ -448,8 +508,8 @@ def train_d(rng, state, batch, generator, discriminator, config, grad_sync=None,
     if do_prefetch and _PREFETCH_AT_START and not deferred_in:
         prefetch()
         early = False
-    state, out, dld, _, _, d_tape, _new_g_stats, new_sn, _ = _forward(rng, config, state, batch, g, d, need_g_tape=False,
-                                                                      after_trunk=prefetch if early else None, want_metrics=False)
+    state, out, dld, _, _, d_tape, _new_g_stats, new_sn, _, _ = _forward(rng, config, state, batch, g, d, need_g_tape=False,
+                                                                         after_trunk=prefetch if early else None, want_metrics=False)
     keep_async = getattr(ops, "wgrad_async", False)
     if (_ASYNC_WGRAD_D or grad_sync is not None) and hasattr(ops, "wgrad_async"):
         ops.wgrad_async = True
@@ -494,19 +554,23 @@ def train_g_d(rng, state, batch, generator, discriminator, config, additional_da
     stats = additional_data.get("statistics")        # (create_additional_data adds it for config.train_statistics)
     if stats is not None:
         stats.bind(ops, d_arena, g_arena)
-    state, out, dld, dlg, g_tape, d_tape, new_g_stats, new_sn, pre = _forward(rng, config, state, batch, g, d,
-                                                                              need_g_tape=True, image_model=image_model, stats=stats)
+    clip = additional_data["clip_guidance"] if clip_guidance_weight(config) > 0.0 else None
+    state, out, dld, dlg, g_tape, d_tape, new_g_stats, new_sn, pre, cpre = _forward(rng, config, state, batch, g, d, need_g_tape=True,
+                                                                                    image_model=image_model, stats=stats, clip=clip)
     b = g_tape["b"]
     d_scale = g_scale = 1.0
-    c_pre = None
+    c_pre = c_clip = None
 
     def image_pullback(dlg_fake):
         """pullback (0, 1) down to the generated images: the discriminator's g-stream plus, with
         ``pretrained_image_contrastive``, the frozen ResNet-50 term (xmc_gan.py:148-154)"""
-        nonlocal c_pre
+        nonlocal c_pre, c_clip
         dimg = _augment_pullback(ops, d_tape, d.backward_g(d_tape, dlg_fake))
         if pre is not None:
             c_pre, pull = _pretrained_loss(ops, *pre, b)
+            ops.add_into(dimg, pull())
+        if cpre is not None:                         # + lambda * the frozen-CLIP image-text term (config.clip_guidance_weight)
+            c_clip, pull = _clip_loss(ops, config, clip, cpre)
             ops.add_into(dimg, pull())
         return dimg
     excl = grad_sync is not None and getattr(grad_sync, "exclusive", False)
@@ -538,9 +602,19 @@ def train_g_d(rng, state, batch, generator, discriminator, config, additional_da
                 res_done = ops.record_event()
             side = ops._sides[0]
             dres.record_stream(side)
-            with torch.cuda.stream(side):                                    # (no wait for the main stream: only for the event)
+            dclip = clip_done = None
+            if cpre is not None:
+                # + the CLIP part, on the main stream behind the ResNet part (its forward ran on the side stream: the join above)
+                c_clip, pull = _clip_loss(ops, config, clip, cpre)
+                dclip = pull()
+                clip_done = ops.record_event()
+                dclip.record_stream(side)
+            with torch.cuda.stream(side):                                    # (no wait for the main stream: only for the events)
                 ops.wait_event(res_done)
                 ops.add_into(dimg, dres)
+                if dclip is not None:
+                    ops.wait_event(clip_done)
+                    ops.add_into(dimg, dclip)
                 g.backward(g_tape, dimg, on_ready)                           #                  G part
         else:
             with ops.side():                                   # (stream graph main -> {side, wgrad}: no cross edges)
@@ -573,7 +647,7 @@ def train_g_d(rng, state, batch, generator, discriminator, config, additional_da
             grad_sync.wait("d")
             grad_sync.wait("g")
         return _finish_g_d(ops, state, config, out, c_pre, new_g_stats, new_sn, d_scale, g_scale, grad_sync, _fix_args(d),
-                           d_updated=d_updated, nets=(g, d), stats=stats)
+                           d_updated=d_updated, nets=(g, d), stats=stats, c_clip=c_clip)
     keep_async = getattr(ops, "wgrad_async", False)
     if grad_sync is not None and hasattr(ops, "wgrad_async"):
         ops.wgrad_async = True               # data-parallel schedule: weight gradients beside the dgrad chain
@@ -581,8 +655,8 @@ def train_g_d(rng, state, batch, generator, discriminator, config, additional_da
     d.backward_d(d_tape, dld, **d_ready)                                     # pullback (1, 0)
     if grad_sync is not None and not excl:
         d_scale = 1.0 / grad_sync.world if d_sent() else grad_sync.all_reduce(d_arena.grads, "d")   # overlaps the g-stream below
-    if pre is not None and getattr(ops, "_side", None) is not None:
-        ops.join_side()                                                      # the ResNet-50 forward _forward put on the side stream
+    if (pre is not None or cpre is not None) and getattr(ops, "_side", None) is not None:
+        ops.join_side()                                                      # the frozen critics' forwards _forward put on the side stream
     dimg = image_pullback(dlg[b:].contiguous())                              # pullback (0, 1), D (+ ResNet) part
     on_ready = None
     if grad_sync is not None and not excl:
@@ -601,13 +675,14 @@ def train_g_d(rng, state, batch, generator, discriminator, config, additional_da
         grad_sync.wait("d")
         grad_sync.wait("g")
     return _finish_g_d(ops, state, config, out, c_pre, new_g_stats, new_sn, d_scale, g_scale, grad_sync, _fix_args(d), nets=(g, d),
-                       stats=stats)
+                       stats=stats, c_clip=c_clip)
 
 
 def _finish_g_d(ops, state, config, out, c_pre, new_g_stats, new_sn, d_scale, g_scale, grad_sync, fix_args=None, d_updated=False,
-                nets=(None, None), stats=None):
+                nets=(None, None), stats=None, c_clip=None):
     """Optimiser updates, EMA, new state and metrics of train_g_d (xmc_gan.py:170-190).  ``d_updated``: the caller already
-    applied D's update (beside the generator's backward pass).  ``stats``: the step's ``TrainStatistics`` or None."""
+    applied D's update (beside the generator's backward pass).  ``stats``: the step's ``TrainStatistics`` or None.  ``c_clip``:
+    the unweighted CLIP image-text term (config.clip_guidance_weight) or None."""
     if grad_sync is not None:
         grad_sync.wait("d")
     if not d_updated:
@@ -629,6 +704,9 @@ def _finish_g_d(ops, state, config, out, c_pre, new_g_stats, new_sn, d_scale, g_
         metrics["g_loss"] = metrics["g_loss"] + c_pre[0]
     else:
         metrics["c_loss_g_pretrained"] = torch.zeros((), device=out["d_loss"].device)
+    if c_clip is not None:                                                   # (not in the reference) g_loss += lambda * c_clip
+        metrics[CLIP_METRIC_KEY] = c_clip[0]
+        metrics["g_loss"] = metrics["g_loss"] + clip_guidance_weight(config) * c_clip[0]
     if grad_sync is not None:                # TrainMetrics.gather_from_model_output (xmc_gan.py:185-190): mean over replicas
         metrics = grad_sync.mean_metrics(metrics)
     return new_state, metrics
