@@ -38,7 +38,7 @@ extern "C" {
 #define XMC_F32 0
 #define XMC_BF16 1
 
-#define XMC_ABI_VERSION 35
+#define XMC_ABI_VERSION 36
 int xmc_abi_version(void);
 
 /* Launch-heuristic knobs -- split-K workgroup targets and tile-selection thresholds whose defaults were A/B'd inside the
@@ -1020,6 +1020,47 @@ int xmc_ln_bwd_add(const float* x, const float* pos, const float* gamma, const f
 int xmc_bias_quick_gelu_bwd(const float* x, const float* bias, const float* dy, float* dv, int32_t rows, int32_t f, void* stream);
 int xmc_clip_preprocess_bwd(const float* dpatches, void* dimages, int32_t n, int32_t hw, int32_t s, int32_t p, const float* std3,
                             int32_t dtype, void* stream);
+
+/* ---- skipping optimiser updates with non-finite gradients (config.skip_nonfinite_updates; libml/nonfinite_guard.py;
+ *      csrc/nonfinite_guard.hip and the GUARD instantiations of the optimiser kernels, ABI 36) ----
+ * A half step of training becomes a transaction: one verdict, taken on the device after its backward passes, decides whether
+ * ALL of its state changes are applied or none.
+ *  - xmc_nonfinite_verdict scans nseg (1 .. XMC_NONFINITE_MAX_SEGMENTS) float32 segments: `ptrs` is a HOST array of nseg device
+ *    pointers, `n_host` a HOST array of their element counts (both passed to the kernel by value; a count may be 0, and then the
+ *    pointer is not read; every other pointer is 16-byte aligned, XMC_EINVAL otherwise).  An element is bad when its exponent bits
+ *    are all ones (NaN, +inf, -inf; denormals and 0x7f7fffff are fine).  Two launches, no atomics: chunks of 8192 elements are
+ *    dealt round-robin to at most 1024 workgroups, each of which writes one (count, first segment) pair into the workspace `ws`
+ *    (xmc_nonfinite_verdict_workspace_bytes of the same n_host, 16-byte aligned); one workgroup adds the pairs and writes
+ *        verdict[0] = 1 if any element was bad, else 0;   verdict[1] = the number of bad elements (saturating);
+ *        verdict[2] = the index of the first segment that held one, or -1;   verdict[3] = 0
+ *    and updates the persistent counters[4] (the caller zeroes them once):
+ *        [0] += 1 on a bad verdict (half steps skipped in total);   [1] = the current run of consecutive bad verdicts (0 after a
+ *        clean one);   [2] = max([2], [1]) (the longest run since the caller last zeroed it);   [3] is not touched.
+ *  - xmc_commit_if: dst[i] = src[i] for i < n unless verdict[0] != 0 (16-byte copies when both pointers allow).
+ *  - xmc_adam_ema_dev_guarded / xmc_adam_ema_dev_sn_guarded / xmc_adam_wprep_tiles_guarded: the entry point of the same name with
+ *    `verdict` in front of `stream`.  verdict[0] == 0: the same arithmetic, bit for bit.  verdict[0] != 0: p, m, v, ema,
+ *    step_state (Adam's t does not advance) and the prepared copies / partial rows are left as they are; the gradient is still
+ *    overwritten with zeros where zero_grads == 1 would do so (zero_grads == 2 and 0 then write nothing).
+ *  - xmc_metrics_accum_if: xmc_metrics_accum unless verdict[0] != 0 (nothing is added, the call is not counted). */
+#define XMC_NONFINITE_MAX_SEGMENTS 8
+int64_t xmc_nonfinite_verdict_workspace_bytes(const int64_t* n_host, int32_t nseg);
+int xmc_nonfinite_verdict(const float* const* ptrs, const int64_t* n_host, int32_t nseg, int32_t* verdict, int32_t* counters,
+                          void* ws, int64_t ws_bytes, void* stream);
+int xmc_commit_if(float* dst, const float* src, int64_t n, const int32_t* verdict, void* stream);
+int xmc_adam_ema_dev_guarded(float* p, const float* g, float* m, float* v, float* ema, int64_t n, float lr, double beta1,
+                             double beta2, float eps, float* step_state, float grad_scale, float ema_decay,
+                             const int32_t* verdict, void* stream);
+int xmc_adam_ema_dev_sn_guarded(float* p, float* g, float* m, float* v, float* ema, int64_t n, float lr, double beta1,
+                                double beta2, float eps, float* step_state, float grad_scale, float ema_decay,
+                                int32_t zero_grads, const void* map, const void* table, int32_t n_entries,
+                                const float* kvec, const float* scal, const float* u, const float* vv,
+                                const int32_t* verdict, void* stream);
+int xmc_adam_wprep_tiles_guarded(const void* table, int32_t n, int32_t blocks, float* p, float* g, float* m, float* v, float* ema,
+                                 float lr, double beta1, double beta2, float eps, const float* step_state, float grad_scale,
+                                 float ema_decay, int32_t zero_grads, const float* kvec, const float* scal, const float* u,
+                                 const float* vv, void* wf_buf, void* wd_buf, void* pf_buf, void* pd_buf, float* part,
+                                 const int32_t* verdict, void* stream);
+int xmc_metrics_accum_if(const float* const* vals, int32_t n, double* sums, int32_t* info, const int32_t* verdict, void* stream);
 
 #ifdef __cplusplus
 }

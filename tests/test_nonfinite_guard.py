@@ -1,0 +1,252 @@
+"""config.skip_nonfinite_updates on the CPU operator tables: a half step whose gradients are not finite commits nothing, a clean
+step behind a skipped one is the clean step, only the bad half is skipped, the switch changes nothing on clean data, the training
+loop survives a poisoned batch (and stops after ``nonfinite_max_consecutive``), ``check_config`` and the replica refusal.
+
+Two tables: ``CpuOps`` (none of the new ops: the product's torch arithmetic, verdict read on the host) and ``CpuOpsGuard``
+(tests/cpu_ops_guard.py: the new entry points restated, Adam's t in a device-side counter).  The poison is a VALUE in an input tensor:
+``z[row, 0] = NaN``."""
+import json
+import os
+
+import numpy as np
+import pytest
+import torch
+
+from tests.cpu_ops import CpuOps
+from tests.cpu_ops_guard import CpuOpsGuard, assert_same, counters, leaves, poison
+from xmcgan_image_generation_amd import synthetic as syn
+from xmcgan_image_generation_amd import train_utils, xmc_gan
+from xmcgan_image_generation_amd.configs import coco_xmc
+from xmcgan_image_generation_amd.nets import xmc_net
+from xmcgan_image_generation_amd.utils import checkpoint, task_manager
+
+KEYS = xmc_gan.METRIC_KEYS
+NOT_STATE = ("g/t", "d/t")
+
+
+def _cfg(**kw):
+    cfg = coco_xmc.get_test_config()
+    cfg.batch_size = 2
+    cfg.update(kw)
+    return cfg
+
+
+def _batch(cfg, seed):
+    return {k: torch.as_tensor(v) for k, v in syn.make_batch(cfg, per_device_batch=cfg.batch_size, seed=seed).items()}
+
+
+@pytest.fixture(params=[CpuOps, CpuOpsGuard], ids=["host-verdict", "device-verdict"])
+def table(request):
+    xmc_net.set_ops_factory(lambda dtype: request.param(dtype))
+    yield request.param
+    xmc_net.set_ops_factory(None)
+
+
+def _warm(cfg, steps=1):
+    """state S: ``steps`` clean steps from the seed-3 initialisation (non-zero moments, Adam's t > 0)"""
+    gen, disc, state = train_utils.create_train_state(cfg, 3)
+    for s in range(1, steps + 1):
+        state, _ = train_utils.train_step(s, state, _batch(cfg, s), xmc_gan, gen, disc, cfg, {})
+    return gen, disc, state
+
+
+def test_poisoned_step_leaves_state_intact(table):
+    cfg = _cfg(skip_nonfinite_updates=True)
+    gen, disc, state = _warm(cfg)
+    before, step = leaves(state), int(state.step)
+    state, _ = train_utils.train_step(9, state, poison(_batch(cfg, 9), cfg, (0, 1)), xmc_gan, gen, disc, cfg, {})
+    assert_same(leaves(state), before)                   # parameters, m, v, EMA, running statistics, u0, Adam's t: the same bits
+    assert int(state.step) == step + 1                   # the batch was consumed
+    assert counters(state) == [2, 2, 2]
+    assert state.guard.verdict.tolist()[0] == 1 and state.guard.verdict.tolist()[2] >= 0
+
+
+def test_poisoned_step_without_the_switch_ruins_the_parameters(table):
+    """what the switch is for (and the test that fails without the feature: there the guarded run above ends like this one)"""
+    cfg = _cfg()
+    gen, disc, state = _warm(cfg)
+    state, _ = train_utils.train_step(9, state, poison(_batch(cfg, 9), cfg, (0, 1)), xmc_gan, gen, disc, cfg, {})
+    assert not bool(torch.isfinite(state.g_optimizer.arena.params).all())
+    assert not bool(torch.isfinite(state.d_optimizer.arena.params).all())
+    assert state.guard is None
+
+
+def test_clean_step_after_skip_equals_clean_step(table):
+    cfg = _cfg(skip_nonfinite_updates=True)
+    x = _batch(cfg, 11)
+    gen, disc, a = _warm(cfg)
+    a, _ = train_utils.train_step(9, a, poison(_batch(cfg, 9), cfg, (0, 1)), xmc_gan, gen, disc, cfg, {})
+    a, ma = train_utils.train_step(10, a, x, xmc_gan, gen, disc, cfg, {})
+    gen_b, disc_b, b = _warm(cfg)                        # S again, from the same seed and the same clean step
+    b, mb = train_utils.train_step(10, b, x, xmc_gan, gen_b, disc_b, cfg, {})
+    assert_same(leaves(a), leaves(b))
+    for k in KEYS:
+        assert np.float32(float(ma[k])).tobytes() == np.float32(float(mb[k])).tobytes(), k
+    assert int(a.step) == int(b.step) + 1
+    assert counters(a) == [2, 0, 2] and counters(b) == [0, 0, 0]
+
+
+def test_only_the_bad_half_is_skipped(table):
+    cfg = _cfg(skip_nonfinite_updates=True)
+    batch = _batch(cfg, 9)
+    gen, disc, state = _warm(cfg)
+    before = leaves(state)
+    state, _ = train_utils.train_step(9, state, poison(batch, cfg, (1,)), xmc_gan, gen, disc, cfg, {})
+    got = leaves(state)
+    gen_b, disc_b, ref = _warm(cfg)                      # train_d alone on the same first half
+    first_half = train_utils.split_input_dict(batch, cfg.d_step_per_g_step)[0]
+    ref = xmc_gan.train_d(9 * cfg.d_step_per_g_step, ref, first_half, gen_b, disc_b, cfg)
+    want = leaves(ref)
+    for k in want:
+        if k.startswith("d/") or k.startswith("sn/"):
+            assert np.array_equal(got[k], want[k]), k    # D = what train_d alone gives
+        else:
+            assert np.array_equal(got[k], before[k]), k  # G, EMA and the BatchNorm statistics unchanged
+    assert not np.array_equal(got["d/params"], before["d/params"]) and int(got["d/t"]) == int(before["d/t"]) + 1
+    assert counters(state) == [1, 1, 1]
+    assert state.guard.verdict.tolist()[0] == 1
+
+
+def test_switch_on_with_clean_data_is_bit_equal_to_switch_off(table):
+    runs = []
+    for on in (False, True):
+        cfg = _cfg(skip_nonfinite_updates=on)
+        gen, disc, state = train_utils.create_train_state(cfg, 3)
+        metrics = []
+        for s in range(1, 4):
+            state, m = train_utils.train_step(s, state, _batch(cfg, s), xmc_gan, gen, disc, cfg, {})
+            metrics.append({k: np.float32(float(m[k])).tobytes() for k in KEYS})
+        runs.append((leaves(state), metrics, int(state.step)))
+    assert_same(runs[1][0], runs[0][0])
+    assert runs[1][1] == runs[0][1] and runs[1][2] == runs[0][2] == 3
+    assert int(runs[1][0]["g/t"]) == 3 and int(runs[1][0]["d/t"]) == 6
+
+
+# ---------------------------------------------------------------------------------------------------------------- the loop
+def _datasets(poisoned):
+    def hook(config, data_rng, start_step, rank, world, device):
+        def batches():
+            s = start_step
+            while True:
+                b = _batch(config, s)
+                yield poison(b, config, (0, 1)) if (poisoned == "all" or s in poisoned) else b
+                s += 1
+        return batches(), iter(()), 1000
+    return hook
+
+
+def test_train_survives_one_poisoned_batch(table, tmp_path):
+    cfg = _cfg(skip_nonfinite_updates=True, num_train_steps=5, checkpoint_every_steps=5, eval_every_steps=3)
+    state = train_utils.train(cfg, str(tmp_path), datasets=_datasets({2}))
+    assert int(state.step) == 5
+    lines = [json.loads(l) for l in open(tmp_path / "metrics.jsonl")]
+    assert [l["step"] for l in lines] == [3, 5]
+    assert [l["guard/skipped_half_steps"] for l in lines] == [2, 0]      # window counts: both half steps of step 2, then none
+    assert [l["guard/longest_run"] for l in lines] == [2, 0]
+    for line in lines:
+        assert sorted(line) == sorted(KEYS + ("step", "guard/skipped_half_steps", "guard/longest_run"))
+        assert all(np.isfinite(line[k]) for k in KEYS)
+    # the first window's means are those of its two applied steps: a plain eager loop over steps 1 and 3 on the same state
+    gen, disc, ref = train_utils.create_train_state(cfg, train_utils.rng_streams(cfg.seed)["model"])
+    per_step = {}
+    for s in range(1, 4):
+        b = poison(_batch(cfg, s), cfg, (0, 1)) if s == 2 else _batch(cfg, s)
+        ref, m = train_utils.train_step(train_utils.fold_in(train_utils.rng_streams(cfg.seed)["train"], s), ref, b, xmc_gan, gen, disc,
+                                        cfg, {})
+        per_step[s] = m
+    for k in KEYS:
+        want = (np.float64(np.float32(float(per_step[1][k]))) + np.float64(np.float32(float(per_step[3][k])))) / 2
+        assert lines[0][k] == float(want), k
+    # the checkpoint: Adam's t = the number of APPLIED updates (4 of 5 steps), the counters travel
+    paths = task_manager.list_checkpoints(str(tmp_path / "checkpoints-0"))
+    assert [os.path.basename(p) for p in paths] == ["ckpt-1.flax"]
+    _, _, fresh = train_utils.create_train_state(cfg, 99)
+    fresh = checkpoint.restore(paths[0], fresh)
+    assert int(fresh.step) == 5
+    assert fresh.g_optimizer.arena.opt_step == 4 and fresh.d_optimizer.arena.opt_step == 8
+    assert counters(fresh) == [2, 0, 0]
+    assert bool(torch.isfinite(fresh.g_optimizer.arena.params).all()) and bool(torch.isfinite(fresh.d_optimizer.arena.params).all())
+
+
+def test_train_stops_after_max_consecutive_skips(table, tmp_path):
+    cfg = _cfg(skip_nonfinite_updates=True, nonfinite_max_consecutive=2, num_train_steps=4, checkpoint_every_steps=100,
+               eval_every_steps=2)
+    with pytest.raises(FloatingPointError, match="consecutive half steps"):
+        train_utils.train(cfg, str(tmp_path), datasets=_datasets("all"))
+    assert not os.path.exists(tmp_path / "checkpoints-0") or not task_manager.list_checkpoints(str(tmp_path / "checkpoints-0"))
+
+
+def test_switch_off_writes_no_guard_scalars(table, tmp_path):
+    cfg = _cfg(num_train_steps=1, checkpoint_every_steps=1, eval_every_steps=1)
+    train_utils.train(cfg, str(tmp_path), datasets=_datasets(set()))
+    (line,) = [json.loads(l) for l in open(tmp_path / "metrics.jsonl")]
+    assert sorted(line) == sorted(KEYS + ("step",))
+    data = open(task_manager.list_checkpoints(str(tmp_path / "checkpoints-0"))[0], "rb").read()
+    assert "nonfinite_guard" not in checkpoint.msgpack_restore(data)
+
+
+# ----------------------------------------------------------------------------------------------------------- configuration
+@pytest.mark.parametrize("key, value", [("skip_nonfinite_updates", 1), ("skip_nonfinite_updates", "yes"),
+                                        ("nonfinite_max_consecutive", 0), ("nonfinite_max_consecutive", -3),
+                                        ("nonfinite_max_consecutive", 2.5), ("nonfinite_max_consecutive", True),
+                                        ("nonfinite_max_consecutive", None)])
+def test_check_config_rejects_bad_values(key, value):
+    with pytest.raises(ValueError, match=key):
+        xmc_net.check_config(_cfg(**{key: value}))
+
+
+def test_check_config_accepts_the_two_keys():
+    xmc_net.check_config(_cfg())
+    xmc_net.check_config(_cfg(skip_nonfinite_updates=True, nonfinite_max_consecutive=1))
+    xmc_net.check_config(_cfg(skip_nonfinite_updates=False, nonfinite_max_consecutive=100))
+
+
+def test_train_step_refuses_replicas_with_the_switch_on(table):
+    cfg = _cfg(skip_nonfinite_updates=True)
+    gen, disc, state = train_utils.create_train_state(cfg, 3)
+    before = leaves(state)
+    with pytest.raises(ValueError, match="skip_nonfinite_updates"):
+        train_utils.train_step(1, state, _batch(cfg, 1), xmc_gan, gen, disc, cfg, {}, grad_sync=object())
+    assert_same(leaves(state), before)
+    with pytest.raises(ValueError, match="skip_nonfinite_updates"):
+        xmc_gan.train_d(1, state, train_utils.split_input_dict(_batch(cfg, 1), 2)[0], gen, disc, cfg, grad_sync=object())
+
+
+# ------------------------------------------------------------------------------------------------------- the guard's own code
+def test_torch_verdict_and_counters():
+    from xmcgan_image_generation_amd.libml.nonfinite_guard import NonfiniteGuard
+    g = NonfiniteGuard(torch.device("cpu"))
+    ops = CpuOps()
+    tiny = torch.tensor([1e-45, -0.0, 3.4028234663852886e38, -3.4028234663852886e38])
+    assert g.judge(ops, [tiny, torch.zeros(0), torch.ones(5)]).tolist() == [0, 0, -1, 0] and g.counters.tolist() == [0, 0, 0, 0]
+    bad = torch.ones(7)
+    bad[6] = float("-inf")
+    bad[0] = float("nan")
+    assert g.judge(ops, [tiny, bad]).tolist() == [1, 2, 1, 0] and g.counters.tolist() == [1, 1, 1, 0]
+    assert g.judge(ops, [bad]).tolist() == [1, 2, 0, 0] and g.counters.tolist() == [2, 2, 2, 0]
+    dst = torch.zeros(7)
+    g.commit(ops, dst, torch.ones(7))
+    assert not dst.any()                                 # a bad verdict commits nothing
+    assert g.judge(ops, [tiny]).tolist() == [0, 0, -1, 0] and g.counters.tolist() == [2, 0, 2, 0]
+    g.commit(ops, dst, torch.ones(7))
+    assert dst.eq(1).all()
+    g.reset_longest()
+    assert g.read() == dict(skipped=2, run=0, longest=0)
+    with pytest.raises(ValueError):
+        g.judge(ops, [torch.ones(1)] * 9)
+    with pytest.raises(ValueError):
+        g.judge(ops, [torch.ones(2, dtype=torch.float64)])
+    h = NonfiniteGuard(torch.device("cpu"))
+    h.load_state_dict(g.state_dict())
+    assert h.counters.tolist() == g.counters.tolist()
+
+
+def test_sync_opt_step_reads_the_device_counter(table):
+    cfg = _cfg(skip_nonfinite_updates=True)
+    gen, disc, state = _warm(cfg)
+    state, _ = train_utils.train_step(9, state, poison(_batch(cfg, 9), cfg, (0, 1)), xmc_gan, gen, disc, cfg, {})
+    ga, da = state.g_optimizer.arena, state.d_optimizer.arena
+    if table is CpuOpsGuard:                             # the host mirror ran ahead: an upper bound between syncs
+        assert (ga.opt_step, da.opt_step) == (2, 4)
+    assert (ga.sync_opt_step(), da.sync_opt_step()) == (1, 2)
+    assert (ga.opt_step, da.opt_step) == (1, 2)

@@ -18,7 +18,7 @@ LIB_PATH = os.path.join(_HERE, "libxmcgan_hip.so")
 PROBE_LIB_PATH = os.path.join(_HERE, "libxmc_probe.so")
 
 XMC_F32, XMC_BF16 = 0, 1
-ABI_VERSION = 35
+ABI_VERSION = 36
 
 # xmc_conv_desc.w_packed and xmc_wgrad_desc.variant: the names of include/xmcgan_hip.h (tests/test_conv_geometry.py keeps them equal)
 XMC_CONV_PACKED, XMC_CONV_PHASE, XMC_CONV_PHASE_PER_WG, XMC_CONV_COMPACT, XMC_CONV_NO_PX128 = 0x1, 0x10, 0x20, 0x40, 0x80
@@ -73,6 +73,7 @@ class TrainStatsArgs(C.Structure):   # mirrors xmc_train_stats_args
 
 XMC_LN_BWD_ROWS, XMC_LN_BWD_GATHER, XMC_LN_BWD_VISION = 0, 1, 2
 TRAIN_STATS_N = 25                   # XMC_TRAIN_STATS_N
+NONFINITE_MAX_SEGMENTS = 8           # XMC_NONFINITE_MAX_SEGMENTS
 CACHE_PLAN_STRIDE = 8                 # XMC_CACHE_PLAN_STRIDE
 
 _P, _I, _L, _F = C.c_void_p, C.c_int32, C.c_int64, C.c_float
@@ -223,6 +224,15 @@ SIGNATURES = {
     "xmc_diffaug_workspace_bytes": [_I, _I, _I],
     "xmc_diffaug_fwd": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P],
     "xmc_diffaug_bwd": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P],
+    "xmc_nonfinite_verdict_workspace_bytes": [_P, _I],
+    "xmc_nonfinite_verdict": [_P, _P, _I, _P, _P, _P, _L, _P],
+    "xmc_commit_if": [_P, _P, _L, _P, _P],
+    "xmc_adam_ema_dev_guarded": [_P, _P, _P, _P, _P, _L, _F, C.c_double, C.c_double, _F, _P, _F, _F, _P, _P],
+    "xmc_adam_ema_dev_sn_guarded": [_P, _P, _P, _P, _P, _L, _F, C.c_double, C.c_double, _F, _P, _F, _F, _I, _P, _P, _I, _P, _P, _P, _P, _P,
+                                    _P],
+    "xmc_adam_wprep_tiles_guarded": [_P, _I, _I, _P, _P, _P, _P, _P, _F, C.c_double, C.c_double, _F, _P, _F, _F, _I, _P, _P, _P, _P, _P, _P,
+                                     _P, _P, _P, _P, _P],
+    "xmc_metrics_accum_if": [_P, _I, _P, _P, _P, _P],
 }
 
 # diagnostic probes: include/xmc_probe.h, libxmc_probe.so (csrc_probe/) -- outside the product ABI
@@ -237,7 +247,7 @@ PROBE_SIGNATURES = {
 
 _INT64_RETURNS = ("xmc_conv2d_mx8_workspace_bytes", "xmc_conv2d_mx8_phase_in_workspace_bytes", "xmc_conv2d_workspace_bytes", "xmc_bn_stats_ws_floats", "xmc_cbn_bwd_sums_ws_floats",
                   "xmc_conv2d_wgrad_workspace_bytes", "xmc_reduce_mid_ws_floats", "xmc_gemm_ws_floats", "xmc_segment_sumsq_ws_bytes", "xmc_sample_metrics_ws_bytes",
-                  "xmc_diffaug_workspace_bytes")
+                  "xmc_diffaug_workspace_bytes", "xmc_nonfinite_verdict_workspace_bytes")
 _lib = None
 
 

@@ -171,7 +171,10 @@ __global__ __launch_bounds__(256) void add_kernel(const T* __restrict__ a, const
 // half step).  `map` has one int16 per 64 arena elements (every tensor starts 64-aligned: ParamArena.ALIGN): the index of the
 // spectral table entry that owns them, or -1.  zero_g: the consumed gradient is overwritten with zeros (the next half step
 // accumulates into a clean arena without a separate fill).
-template <bool FIX>
+// GUARD (config.skip_nonfinite_updates; xmc_*_guarded): verdict[0] != 0 (xmc_nonfinite_verdict found a NaN or an infinity in what
+// this half step would commit) leaves p, m, v and ema as they are; the gradient is still zeroed where zero_g == 1 would zero
+// it, so that the bad values do not reach the next half step.  The GUARD = false instantiation is the kernel as it was.
+template <bool FIX, bool GUARD = false>
 __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, float* __restrict__ g,
                                                    float* __restrict__ m, float* __restrict__ v,
                                                    float* __restrict__ ema, long long n, float lr, float b1,
@@ -179,7 +182,19 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, float*
                                                    const float* __restrict__ corr, int zero_g, const short* __restrict__ map,
                                                    const xmc_sn_entry* __restrict__ tab, const float* __restrict__ kvec,
                                                    const float* __restrict__ scal, const float* __restrict__ uvec,
-                                                   const float* __restrict__ vvec) {
+                                                   const float* __restrict__ vvec, const int* __restrict__ verdict = nullptr) {
+    if constexpr (GUARD) {
+        if (verdict[0] != 0) {                       // skipped half step (uniform over the grid)
+            if (zero_g != 1) return;
+            const long long q4 = n >> 2;
+            for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < q4; i += (long long)gridDim.x * 256) {
+                if (map && map[i >> 4] == -2) continue;
+                reinterpret_cast<float4*>(g)[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+            }
+            if (blockIdx.x == 0 && threadIdx.x < (n & 3)) g[(q4 << 2) + threadIdx.x] = 0.f;
+            return;
+        }
+    }
     if (corr) { ic1 = corr[1]; ic2 = corr[2]; }      // device-side step counter (hipGraph replay): see adam_advance_kernel
     const long long n4 = n >> 2;
     for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n4; i += (long long)gridDim.x * 256) {
@@ -415,14 +430,18 @@ extern "C" int xmc_adam_ema(float* p, const float* g, float* m, float* v, float*
     hipLaunchKernelGGL((adam_kernel<false>), dim3(grid_for(n / 4 + 1)), dim3(256), 0, static_cast<hipStream_t>(stream), p, const_cast<float*>(g),
                        m, v, ema, (long long)n, lr, beta1, beta2, eps, 1.f / c1, 1.f / c2, grad_scale, ema_decay,
                        static_cast<const float*>(nullptr), 0, (const short*)nullptr, (const xmc_sn_entry*)nullptr, (const float*)nullptr,
-                       (const float*)nullptr, (const float*)nullptr, (const float*)nullptr);
+                       (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, (const int*)nullptr);
     XMC_LAUNCH_RET();
 }
 
 // step counter of one optimiser kept in DEVICE memory: state[0] = t (int32 bits), state[1] = 1 / (1 - beta1^t),
 // state[2] = 1 / (1 - beta2^t).  One thread advances t and refreshes the two bias corrections in double precision;
 // the Adam kernel launched right behind it reads them -- so a captured hipGraph replays the right step.
-__global__ void adam_advance_kernel(float* state, double b1, double b2) {
+template <bool GUARD = false>
+__global__ void adam_advance_kernel(float* state, double b1, double b2, const int* verdict = nullptr) {
+    if constexpr (GUARD) {
+        if (verdict[0] != 0) return;                 // a skipped update does not advance Adam's t
+    }
     const int t = __float_as_int(state[0]) + 1;
     state[0] = __int_as_float(t);
     state[1] = (float)(1.0 / (1.0 - pow(b1, (double)t)));
@@ -436,11 +455,11 @@ extern "C" int xmc_adam_ema_dev(float* p, const float* g, float* m, float* v, fl
     XMC_REQUIRE(((uintptr_t)p % 16) == 0 && ((uintptr_t)g % 16) == 0 && ((uintptr_t)m % 16) == 0 &&
                 ((uintptr_t)v % 16) == 0 && (ema == nullptr || ((uintptr_t)ema % 16) == 0));
     hipStream_t s = static_cast<hipStream_t>(stream);
-    hipLaunchKernelGGL(adam_advance_kernel, dim3(1), dim3(1), 0, s, step_state, beta1, beta2);
+    hipLaunchKernelGGL((adam_advance_kernel<false>), dim3(1), dim3(1), 0, s, step_state, beta1, beta2, (const int*)nullptr);
     hipLaunchKernelGGL((adam_kernel<false>), dim3(grid_for(n / 4 + 1)), dim3(256), 0, s, p, const_cast<float*>(g), m, v, ema, (long long)n, lr,
                        (float)beta1, (float)beta2, eps, 1.f, 1.f, grad_scale, ema_decay, static_cast<const float*>(step_state),
                        0, (const short*)nullptr, (const xmc_sn_entry*)nullptr, (const float*)nullptr, (const float*)nullptr,
-                       (const float*)nullptr, (const float*)nullptr);
+                       (const float*)nullptr, (const float*)nullptr, (const int*)nullptr);
     XMC_LAUNCH_RET();
 }
 
@@ -457,16 +476,59 @@ extern "C" int xmc_adam_ema_dev_sn(float* p, float* g, float* m, float* v, float
                 ((uintptr_t)v % 16) == 0 && (ema == nullptr || ((uintptr_t)ema % 16) == 0));
     XMC_REQUIRE(!table || (map && n_entries > 0 && kvec && scal && u && vv));     // (map without table: skip marks only)
     hipStream_t s = static_cast<hipStream_t>(stream);
-    hipLaunchKernelGGL(adam_advance_kernel, dim3(1), dim3(1), 0, s, step_state, beta1, beta2);
+    hipLaunchKernelGGL((adam_advance_kernel<false>), dim3(1), dim3(1), 0, s, step_state, beta1, beta2, (const int*)nullptr);
     if (table)
         hipLaunchKernelGGL((adam_kernel<true>), dim3(grid_for(n / 4 + 1)), dim3(256), 0, s, p, g, m, v, ema, (long long)n, lr,
                            (float)beta1, (float)beta2, eps, 1.f, 1.f, grad_scale, ema_decay, static_cast<const float*>(step_state),
-                           zero_grads, static_cast<const short*>(map), static_cast<const xmc_sn_entry*>(table), kvec, scal, u, vv);
+                           zero_grads, static_cast<const short*>(map), static_cast<const xmc_sn_entry*>(table), kvec, scal, u, vv,
+                           (const int*)nullptr);
     else
         hipLaunchKernelGGL((adam_kernel<false>), dim3(grid_for(n / 4 + 1)), dim3(256), 0, s, p, g, m, v, ema, (long long)n, lr,
                            (float)beta1, (float)beta2, eps, 1.f, 1.f, grad_scale, ema_decay, static_cast<const float*>(step_state),
                            zero_grads, static_cast<const short*>(map), (const xmc_sn_entry*)nullptr, (const float*)nullptr,
-                           (const float*)nullptr, (const float*)nullptr, (const float*)nullptr);
+                           (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, (const int*)nullptr);
+    XMC_LAUNCH_RET();
+}
+
+// ---- config.skip_nonfinite_updates: the guarded forms.  Same arguments as the entry points above plus `verdict` (the int32[4]
+// of xmc_nonfinite_verdict, read on the device): verdict[0] == 0 runs the same arithmetic, bit for bit; verdict[0] != 0 leaves
+// p, m, v, ema and step_state untouched and only zeroes the gradient where the unguarded form would (zero_grads == 1).
+extern "C" int xmc_adam_ema_dev_guarded(float* p, const float* g, float* m, float* v, float* ema, int64_t n, float lr, double beta1,
+                                        double beta2, float eps, float* step_state, float grad_scale, float ema_decay,
+                                        const int32_t* verdict, void* stream) {
+    XMC_REQUIRE(p && g && m && v && n > 0 && step_state && verdict && ((uintptr_t)verdict % 4) == 0);
+    XMC_REQUIRE(((uintptr_t)p % 16) == 0 && ((uintptr_t)g % 16) == 0 && ((uintptr_t)m % 16) == 0 &&
+                ((uintptr_t)v % 16) == 0 && (ema == nullptr || ((uintptr_t)ema % 16) == 0));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    hipLaunchKernelGGL((adam_advance_kernel<true>), dim3(1), dim3(1), 0, s, step_state, beta1, beta2, static_cast<const int*>(verdict));
+    hipLaunchKernelGGL((adam_kernel<false, true>), dim3(grid_for(n / 4 + 1)), dim3(256), 0, s, p, const_cast<float*>(g), m, v, ema,
+                       (long long)n, lr, (float)beta1, (float)beta2, eps, 1.f, 1.f, grad_scale, ema_decay, static_cast<const float*>(step_state),
+                       0, (const short*)nullptr, (const xmc_sn_entry*)nullptr, (const float*)nullptr, (const float*)nullptr,
+                       (const float*)nullptr, (const float*)nullptr, static_cast<const int*>(verdict));
+    XMC_LAUNCH_RET();
+}
+
+extern "C" int xmc_adam_ema_dev_sn_guarded(float* p, float* g, float* m, float* v, float* ema, int64_t n, float lr, double beta1,
+                                           double beta2, float eps, float* step_state, float grad_scale, float ema_decay,
+                                           int32_t zero_grads, const void* map, const void* table, int32_t n_entries,
+                                           const float* kvec, const float* scal, const float* u, const float* vv,
+                                           const int32_t* verdict, void* stream) {
+    XMC_REQUIRE(p && g && m && v && n > 0 && step_state && verdict && ((uintptr_t)verdict % 4) == 0);
+    XMC_REQUIRE(((uintptr_t)p % 16) == 0 && ((uintptr_t)g % 16) == 0 && ((uintptr_t)m % 16) == 0 &&
+                ((uintptr_t)v % 16) == 0 && (ema == nullptr || ((uintptr_t)ema % 16) == 0));
+    XMC_REQUIRE(!table || (map && n_entries > 0 && kvec && scal && u && vv));     // (map without table: skip marks only)
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    hipLaunchKernelGGL((adam_advance_kernel<true>), dim3(1), dim3(1), 0, s, step_state, beta1, beta2, static_cast<const int*>(verdict));
+    if (table)
+        hipLaunchKernelGGL((adam_kernel<true, true>), dim3(grid_for(n / 4 + 1)), dim3(256), 0, s, p, g, m, v, ema, (long long)n, lr,
+                           (float)beta1, (float)beta2, eps, 1.f, 1.f, grad_scale, ema_decay, static_cast<const float*>(step_state),
+                           zero_grads, static_cast<const short*>(map), static_cast<const xmc_sn_entry*>(table), kvec, scal, u, vv,
+                           static_cast<const int*>(verdict));
+    else
+        hipLaunchKernelGGL((adam_kernel<false, true>), dim3(grid_for(n / 4 + 1)), dim3(256), 0, s, p, g, m, v, ema, (long long)n, lr,
+                           (float)beta1, (float)beta2, eps, 1.f, 1.f, grad_scale, ema_decay, static_cast<const float*>(step_state),
+                           zero_grads, static_cast<const short*>(map), (const xmc_sn_entry*)nullptr, (const float*)nullptr,
+                           (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, static_cast<const int*>(verdict));
     XMC_LAUNCH_RET();
 }
 
@@ -476,8 +538,13 @@ extern "C" int xmc_adam_ema_dev_sn(float* p, float* g, float* m, float* v, float
 // that saw a non-finite value.  Plain loads and stores: launches on one stream are ordered, nothing else touches the buffers.
 struct metric_ptrs { const float* p[8]; };
 
-__global__ void metrics_accum_kernel(metric_ptrs v, int n, double* sums, int* info) {
+// GUARD (xmc_metrics_accum_if): a skipped half step (verdict[0] != 0) adds nothing and is not counted as a call.
+template <bool GUARD = false>
+__global__ void metrics_accum_kernel(metric_ptrs v, int n, double* sums, int* info, const int* verdict = nullptr) {
     if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    if constexpr (GUARD) {
+        if (verdict[0] != 0) return;
+    }
     bool bad = false;
 #pragma unroll
     for (int i = 0; i < 8; ++i) {
@@ -500,7 +567,22 @@ extern "C" int xmc_metrics_accum(const float* const* vals, int32_t n, double* su
         v.p[i] = i < n ? vals[i] : nullptr;
         XMC_REQUIRE(i >= n || (v.p[i] && ((uintptr_t)v.p[i] % 4) == 0));
     }
-    hipLaunchKernelGGL(metrics_accum_kernel, dim3(1), dim3(1), 0, static_cast<hipStream_t>(stream), v, (int)n, sums, info);
+    hipLaunchKernelGGL((metrics_accum_kernel<false>), dim3(1), dim3(1), 0, static_cast<hipStream_t>(stream), v, (int)n, sums, info,
+                       (const int*)nullptr);
+    XMC_LAUNCH_RET();
+}
+
+extern "C" int xmc_metrics_accum_if(const float* const* vals, int32_t n, double* sums, int32_t* info, const int32_t* verdict,
+                                    void* stream) {
+    XMC_REQUIRE(vals && sums && info && n >= 1 && n <= 8 && verdict);
+    XMC_REQUIRE(((uintptr_t)sums % 8) == 0 && ((uintptr_t)info % 4) == 0 && ((uintptr_t)verdict % 4) == 0);
+    metric_ptrs v;
+    for (int i = 0; i < 8; ++i) {
+        v.p[i] = i < n ? vals[i] : nullptr;
+        XMC_REQUIRE(i >= n || (v.p[i] && ((uintptr_t)v.p[i] % 4) == 0));
+    }
+    hipLaunchKernelGGL((metrics_accum_kernel<true>), dim3(1), dim3(1), 0, static_cast<hipStream_t>(stream), v, (int)n, sums, info,
+                       static_cast<const int*>(verdict));
     XMC_LAUNCH_RET();
 }
 

@@ -501,7 +501,9 @@ __global__ __launch_bounds__(256) void wprep_kernel(const WprepEntry* __restrict
 // in (FIX) and the zeroing / keeping of the consumed gradient -- followed by wprep_kernel's emission from the updated tile:
 // the next forward pass finds its copies (and the first product of its power iteration, taken with THIS half step's new u) ready
 // and never reads the float32 masters.  The flat Adam kernel skips these tensors (map value -2).
-template <bool FIX>
+// GUARD (xmc_adam_wprep_tiles_guarded): verdict[0] != 0 leaves p, m, v, ema AND the emitted copies / partial rows as they are
+// (they still describe the parameters, which did not change) and only zeroes the tile's gradient where zero_g == 1 would.
+template <bool FIX, bool GUARD = false>
 __global__ __launch_bounds__(256) void adam_wprep_kernel(const WprepEntry* __restrict__ tab, int n, float* __restrict__ p,
                                                          float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
                                                          float* __restrict__ ema, float lr, float b1, float b2, float eps,
@@ -510,7 +512,7 @@ __global__ __launch_bounds__(256) void adam_wprep_kernel(const WprepEntry* __res
                                                          const float* __restrict__ uvec, const float* __restrict__ vvec,
                                                          bf16_t* __restrict__ wf_buf, bf16_t* __restrict__ wd_buf,
                                                          bf16_t* __restrict__ pf_buf, bf16_t* __restrict__ pd_buf,
-                                                         float* __restrict__ part) {
+                                                         float* __restrict__ part, const int* __restrict__ verdict = nullptr) {
     __shared__ float t9[9][32][33];
     __shared__ float us[32];
     const WprepEntry e = tab[find_wprep(tab, n, blockIdx.x, 0)];
@@ -519,6 +521,16 @@ __global__ __launch_bounds__(256) void adam_wprep_kernel(const WprepEntry* __res
     const int n0 = (b / tc) * 32, c0 = (b % tc) * 32;
     const int tid = threadIdx.x;
     const int row = tid >> 3, c4 = (tid & 7) * 4;
+    if constexpr (GUARD) {
+        if (verdict[0] != 0) {                       // skipped half step (uniform over the grid: no barrier is left waiting)
+            if (zero_g == 1) {
+                const size_t gbase = (size_t)e.w_off + (size_t)(n0 + row) * taps * cin + c0 + c4;
+                for (int tap = 0; tap < taps; ++tap)
+                    *reinterpret_cast<float4*>(g + gbase + (size_t)tap * cin) = make_float4(0.f, 0.f, 0.f, 0.f);
+            }
+            return;
+        }
+    }
     const float ic1 = corr[1], ic2 = corr[2];        // device-side step counter, already advanced (adam_advance_kernel)
     const bool spectral = FIX && (e.flags & 16);
     float ur = 0.f, is = 1.f;
@@ -703,12 +715,39 @@ extern "C" int xmc_adam_wprep_tiles(const void* table, int32_t n, int32_t blocks
     if (fix)
         hipLaunchKernelGGL((adam_wprep_kernel<true>), dim3(blocks), dim3(256), 0, s, tab, n, p, g, m, v, ema, lr, (float)beta1, (float)beta2,
                            eps, step_state, grad_scale, ema_decay, zero_grads, kvec, scal, u, vv, static_cast<bf16_t*>(wf_buf),
-                           static_cast<bf16_t*>(wd_buf), static_cast<bf16_t*>(pf_buf), static_cast<bf16_t*>(pd_buf), part);
+                           static_cast<bf16_t*>(wd_buf), static_cast<bf16_t*>(pf_buf), static_cast<bf16_t*>(pd_buf), part, (const int*)nullptr);
     else
         hipLaunchKernelGGL((adam_wprep_kernel<false>), dim3(blocks), dim3(256), 0, s, tab, n, p, g, m, v, ema, lr, (float)beta1, (float)beta2,
                            eps, step_state, grad_scale, ema_decay, zero_grads, (const float*)nullptr, (const float*)nullptr,
                            (const float*)nullptr, (const float*)nullptr, static_cast<bf16_t*>(wf_buf), static_cast<bf16_t*>(wd_buf),
-                           static_cast<bf16_t*>(pf_buf), static_cast<bf16_t*>(pd_buf), part);
+                           static_cast<bf16_t*>(pf_buf), static_cast<bf16_t*>(pd_buf), part, (const int*)nullptr);
+    XMC_LAUNCH_RET();
+}
+
+// xmc_adam_wprep_tiles under config.skip_nonfinite_updates: `verdict` is the int32[4] of xmc_nonfinite_verdict (device memory)
+extern "C" int xmc_adam_wprep_tiles_guarded(const void* table, int32_t n, int32_t blocks, float* p, float* g, float* m, float* v,
+                                            float* ema, float lr, double beta1, double beta2, float eps, const float* step_state,
+                                            float grad_scale, float ema_decay, int32_t zero_grads, const float* kvec, const float* scal,
+                                            const float* u, const float* vv, void* wf_buf, void* wd_buf, void* pf_buf, void* pd_buf,
+                                            float* part, const int32_t* verdict, void* stream) {
+    XMC_REQUIRE(table && p && g && m && v && step_state && n > 0 && n <= 64 && blocks > 0 && verdict && ((uintptr_t)verdict % 4) == 0);
+    XMC_REQUIRE(sizeof(WprepEntry) == sizeof(xmc_wprep_entry));
+    XMC_REQUIRE(((uintptr_t)p % 16) == 0 && ((uintptr_t)g % 16) == 0 && ((uintptr_t)m % 16) == 0 && ((uintptr_t)v % 16) == 0 &&
+                (ema == nullptr || ((uintptr_t)ema % 16) == 0));
+    const bool fix = kvec != nullptr;
+    XMC_REQUIRE(!fix || (scal && u && vv && part && ((uintptr_t)vv % 16) == 0));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const WprepEntry* tab = static_cast<const WprepEntry*>(table);
+    const int* vd = static_cast<const int*>(verdict);
+    if (fix)
+        hipLaunchKernelGGL((adam_wprep_kernel<true, true>), dim3(blocks), dim3(256), 0, s, tab, n, p, g, m, v, ema, lr, (float)beta1,
+                           (float)beta2, eps, step_state, grad_scale, ema_decay, zero_grads, kvec, scal, u, vv, static_cast<bf16_t*>(wf_buf),
+                           static_cast<bf16_t*>(wd_buf), static_cast<bf16_t*>(pf_buf), static_cast<bf16_t*>(pd_buf), part, vd);
+    else
+        hipLaunchKernelGGL((adam_wprep_kernel<false, true>), dim3(blocks), dim3(256), 0, s, tab, n, p, g, m, v, ema, lr, (float)beta1,
+                           (float)beta2, eps, step_state, grad_scale, ema_decay, zero_grads, (const float*)nullptr, (const float*)nullptr,
+                           (const float*)nullptr, (const float*)nullptr, static_cast<bf16_t*>(wf_buf), static_cast<bf16_t*>(wd_buf),
+                           static_cast<bf16_t*>(pf_buf), static_cast<bf16_t*>(pd_buf), part, vd);
     XMC_LAUNCH_RET();
 }
 

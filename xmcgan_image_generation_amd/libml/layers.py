@@ -149,8 +149,17 @@ class ParamArena:
             self.step_state.view(torch.int32)[0] = int(t)
 
     def note_steps(self, k=1):
-        """The device counter was advanced ``k`` times by the Adam kernels: advance the host mirror."""
+        """The device counter was advanced ``k`` times by the Adam kernels: advance the host mirror.  Under
+        config.skip_nonfinite_updates a skipped update does not advance the device counter: the mirror is then an upper bound
+        until ``sync_opt_step``."""
         self._opt_step += k
+
+    def sync_opt_step(self):
+        """Read Adam's t back from the device counter (a host synchronisation; never inside a graph capture) -> t.  Without a
+        device counter the host value is already exact."""
+        if self.step_state is not None:
+            self._opt_step = int(self.step_state.view(torch.int32)[0])
+        return self._opt_step
 
     # ------------------------------------------------------------------------------ views
     def view(self, path, buf=None):

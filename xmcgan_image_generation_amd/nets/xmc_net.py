@@ -104,6 +104,13 @@ def check_config(config):
         if config.get("device_dataset_cache", False):
             raise ValueError("clip_guidance_weight > 0 is not supported with device_dataset_cache=True: the cache carries no caption "
                              "strings, and the term embeds each training caption's text; train with device_dataset_cache=False")
+    skip = config.get("skip_nonfinite_updates", False)
+    if not isinstance(skip, bool):
+        raise ValueError(f"skip_nonfinite_updates={skip!r} must be True or False")
+    limit = config.get("nonfinite_max_consecutive", 100)
+    if isinstance(limit, bool) or not isinstance(limit, int) or limit < 1:
+        raise ValueError(f"nonfinite_max_consecutive={limit!r} must be an integer >= 1: the run of consecutive skipped half steps at "
+                         "which train() stops (a NaN that persists means the parameters or the data are bad)")
     extras = tuple(config.get("eval_extra_metrics", ()))
     if extras:
         from ..utils.eval_metrics import extra_metric_keys

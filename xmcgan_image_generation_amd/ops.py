@@ -962,6 +962,47 @@ class HipOps:
         ptrs = (C.c_void_p * n)(*[v.data_ptr() for v in vals])
         check(self.lib.xmc_metrics_accum(ptrs, n, _p(sums), _p(info), self._stream()), "xmc_metrics_accum")
 
+    def metrics_accum_if(self, vals, sums, info, verdict):
+        """``metrics_accum`` unless ``verdict[0] != 0`` (read on the device: a skipped half step adds nothing and is not counted)"""
+        n = len(vals)
+        assert 1 <= n <= 8 and sums.dtype == torch.float64 and sums.numel() >= n and sums.is_contiguous()
+        assert info.dtype == torch.int32 and info.numel() >= 2 and info.is_contiguous()
+        assert all(v.dtype == torch.float32 and v.numel() == 1 and v.device == sums.device for v in vals)
+        assert verdict.dtype == torch.int32 and verdict.numel() >= 4 and verdict.device == sums.device
+        ptrs = (C.c_void_p * n)(*[v.data_ptr() for v in vals])
+        check(self.lib.xmc_metrics_accum_if(ptrs, n, _p(sums), _p(info), _p(verdict), self._stream()), "xmc_metrics_accum_if")
+
+    # ------------------------------------------------------------------ config.skip_nonfinite_updates (libml/nonfinite_guard.py)
+    def nonfinite_verdict_ws_bytes(self, lengths):
+        """bytes of workspace ``nonfinite_verdict`` needs for segments of these element counts"""
+        n = (C.c_int64 * len(lengths))(*[int(k) for k in lengths])
+        nbytes = self.lib.xmc_nonfinite_verdict_workspace_bytes(n, len(lengths))
+        check(min(nbytes, 0), "xmc_nonfinite_verdict_workspace_bytes")
+        return nbytes
+
+    def nonfinite_verdict(self, segments, verdict, counters, ws):
+        """verdict (int32[4]) = [any NaN / +-inf in the float32 ``segments`` (1 to 8 contiguous tensors), how many, the first
+        segment that held one or -1, 0]; ``counters`` (int32[4], persistent) = [bad verdicts in total, the current run of them,
+        the longest run, -].  ``ws``: uint8 workspace of ``nonfinite_verdict_ws_bytes``.  Two launches on the current stream, no
+        atomics, no host read (capturable)."""
+        k = len(segments)
+        assert 1 <= k <= _lib.NONFINITE_MAX_SEGMENTS
+        assert all(t.dtype == torch.float32 and t.is_contiguous() and t.device == verdict.device for t in segments)
+        assert verdict.dtype == torch.int32 and verdict.numel() >= 4 and verdict.is_contiguous()
+        assert counters.dtype == torch.int32 and counters.numel() >= 4 and counters.is_contiguous() and ws.dtype == torch.uint8
+        ptrs = (C.c_void_p * k)(*[t.data_ptr() if t.numel() else None for t in segments])
+        n = (C.c_int64 * k)(*[t.numel() for t in segments])
+        check(self.lib.xmc_nonfinite_verdict(ptrs, n, k, _p(verdict), _p(counters), _p(ws), ws.numel(), self._stream()),
+              "xmc_nonfinite_verdict")
+
+    def commit_if(self, dst, src, verdict):
+        """dst = src (float32, same size) unless ``verdict[0] != 0`` -- decided on the device"""
+        assert dst.dtype == torch.float32 and src.dtype == torch.float32 and dst.numel() == src.numel()
+        assert dst.is_contiguous() and src.is_contiguous() and verdict.dtype == torch.int32 and verdict.numel() >= 4
+        if dst.numel():
+            check(self.lib.xmc_commit_if(_p(dst), _p(src), dst.numel(), _p(verdict), self._stream()), "xmc_commit_if")
+        return dst
+
     def segment_sumsq_ws_bytes(self, segs_host, nseg):
         """bytes of workspace ``segment_sumsq`` needs for the HOST table ``segs_host`` (a ctypes int64 array of nseg (offset, length) pairs)"""
         nbytes = self.lib.xmc_segment_sumsq_ws_bytes(segs_host, nseg)
@@ -1529,20 +1570,27 @@ class HipOps:
         return m.to(self.device)
 
     def adam_wprep(self, wp, out, p, g, m, v, ema, step_state, *, lr, beta1, beta2, eps=1e-8, grad_scale=1.0, ema_decay=0.0,
-                   zero_grads=True, fix=None):
+                   zero_grads=True, fix=None, verdict=None):
         """xmc_adam_wprep_tiles: the Adam (+ EMA) update of ``wp``'s weights fused with their preparation into ``out`` = (bufs,
         part); ``step_state`` already advanced by ``adam_ema_dev_sn`` on the same arena (whose map skipped these tensors).
-        ``fix`` = (kvec, scal, u, v) for a spectral arena."""
+        ``fix`` = (kvec, scal, u, v) for a spectral arena.  ``verdict`` (config.skip_nonfinite_updates): the guarded form."""
         bufs, part = out
         fa = tuple(_p(t) for t in fix) if fix is not None else (None, None, None, None)
+        if verdict is not None:
+            check(self.lib.xmc_adam_wprep_tiles_guarded(_p(wp["tab"]), wp["n"], wp["blocks"], _p(p), _p(g), _p(m), _p(v), _p(ema), lr, beta1,
+                                                        beta2, eps, _p(step_state), grad_scale, ema_decay,
+                                                        2 if self.keep_grads else int(bool(zero_grads)), *fa, *[_p(b) for b in bufs],
+                                                        _p(part), _p(verdict), self._stream()), "xmc_adam_wprep_tiles_guarded")
+            return
         check(self.lib.xmc_adam_wprep_tiles(_p(wp["tab"]), wp["n"], wp["blocks"], _p(p), _p(g), _p(m), _p(v), _p(ema), lr, beta1, beta2,
                                             eps, _p(step_state), grad_scale, ema_decay, 2 if self.keep_grads else int(bool(zero_grads)),
                                             *fa, *[_p(b) for b in bufs], _p(part), self._stream()), "xmc_adam_wprep_tiles")
 
     def adam_ema_dev_sn(self, p, g, m, v, ema, step_state, *, lr, beta1, beta2, eps=1e-8, grad_scale=1.0, ema_decay=0.0,
-                        zero_grads=True, fix=None, skip_map=None):
+                        zero_grads=True, fix=None, skip_map=None, verdict=None):
         """adam_ema_dev that zeroes the consumed gradient in place and, with ``fix`` = (map, bank, kvec, scal, u, v), applies the
-        gradient through sigma on the fly; ``skip_map`` (no ``fix``): tensors marked -2 are left alone (``adam_wprep``)"""
+        gradient through sigma on the fly; ``skip_map`` (no ``fix``): tensors marked -2 are left alone (``adam_wprep``).
+        ``verdict`` (config.skip_nonfinite_updates): the guarded form -- verdict[0] != 0 leaves everything but the gradient alone"""
         assert step_state.dtype == torch.float32 and step_state.numel() >= 4
         if fix is not None:
             mp, bank, kvec, scal, u, vv = fix
@@ -1551,6 +1599,12 @@ class HipOps:
             args = (_p(skip_map), None, 0, None, None, None, None)
         else:
             args = (None, None, 0, None, None, None, None)
+        if verdict is not None:
+            check(self.lib.xmc_adam_ema_dev_sn_guarded(_p(p), _p(g), _p(m), _p(v), _p(ema), p.numel(), lr, beta1, beta2, eps,
+                                                       _p(step_state), grad_scale, ema_decay,
+                                                       2 if self.keep_grads else int(bool(zero_grads)), *args, _p(verdict),
+                                                       self._stream()), "xmc_adam_ema_dev_sn_guarded")
+            return not self.keep_grads and bool(zero_grads)
         check(self.lib.xmc_adam_ema_dev_sn(_p(p), _p(g), _p(m), _p(v), _p(ema), p.numel(), lr, beta1, beta2, eps, _p(step_state),
                                            grad_scale, ema_decay, 2 if self.keep_grads else int(bool(zero_grads)), *args, self._stream()),
               "xmc_adam_ema_dev_sn")
@@ -1562,10 +1616,15 @@ class HipOps:
         check(self.lib.xmc_adam_ema(_p(p), _p(g), _p(m), _p(v), _p(ema), p.numel(), lr, beta1, beta2, eps, c1, c2,
                                     grad_scale, ema_decay, self._stream()), "xmc_adam_ema")
 
-    def adam_ema_dev(self, p, g, m, v, ema, step_state, *, lr, beta1, beta2, eps=1e-8, grad_scale=1.0, ema_decay=0.0):
+    def adam_ema_dev(self, p, g, m, v, ema, step_state, *, lr, beta1, beta2, eps=1e-8, grad_scale=1.0, ema_decay=0.0, verdict=None):
         """Adam (+EMA) with the step counter / bias corrections in device memory (``step_state``, 4 float32 slots;
-        advanced by one per call) -- the form a captured hipGraph can replay."""
+        advanced by one per call) -- the form a captured hipGraph can replay.  ``verdict``: the guarded form."""
         assert step_state.dtype == torch.float32 and step_state.numel() >= 4
+        if verdict is not None:
+            check(self.lib.xmc_adam_ema_dev_guarded(_p(p), _p(g), _p(m), _p(v), _p(ema), p.numel(), lr, beta1, beta2, eps,
+                                                    _p(step_state), grad_scale, ema_decay, _p(verdict), self._stream()),
+                  "xmc_adam_ema_dev_guarded")
+            return
         check(self.lib.xmc_adam_ema_dev(_p(p), _p(g), _p(m), _p(v), _p(ema), p.numel(), lr, beta1, beta2, eps,
                                         _p(step_state), grad_scale, ema_decay, self._stream()), "xmc_adam_ema_dev")
 

@@ -47,6 +47,7 @@ class TrainState:
     ema_buffer: Any = None          # flat arena behind ema_params (build-side)
     pending: Any = None             # deferred "wait for the D gradient exchange + Adam" of a train_d (multi-GPU only)
     prefetched_g: Any = None        # (batch identity, (image, new batch_stats, tape)) of the next train_g_d's generator forward (train_d)
+    guard: Any = None               # config.skip_nonfinite_updates: the NonfiniteGuard (verdict + skip counters in device memory)
 
     def replace(self, **kw):
         return dataclasses.replace(self, **kw)
@@ -107,13 +108,15 @@ def create_train_state(config, rng, init_batch=None, ops=None):
     d_vars = discriminator(train=False).init(seed + 1, None)
     g_arena, d_arena = g_vars["params"].arena, d_vars["params"].arena
     ema_buffer = g_arena.params.clone()                                   # ema_params = generator_params (:170)
+    from .libml import nonfinite_guard
+    guard = nonfinite_guard.NonfiniteGuard(ops.device) if nonfinite_guard.enabled(config) else None
     state = TrainState(
         step=0,
         g_optimizer=Optimizer(g_arena, config.g_lr, config.beta1, config.beta2),
         d_optimizer=Optimizer(d_arena, config.d_lr, config.beta1, config.beta2),
         generator_state={"batch_stats": g_vars["batch_stats"]},
         discriminator_state={"spectral_norm_stats": d_vars["spectral_norm_stats"]},
-        ema_params=g_arena.tree(ema_buffer), ema_buffer=ema_buffer)
+        ema_params=g_arena.tree(ema_buffer), ema_buffer=ema_buffer, guard=guard)
     return generator, discriminator, state
 
 
@@ -140,6 +143,10 @@ def train_step(rng, state, batch, gan_model=xmc_gan, generator=None, discriminat
     ``d_aug_host`` (config.diff_augment): the host copy of ``batch["d_aug"]`` when that is a device tensor the caller cannot have
     read back here (``GraphedTrainStep``'s capture); otherwise it is made from the batch."""
     n = config.d_step_per_g_step
+    if grad_sync is not None and config.get("skip_nonfinite_updates", False):
+        raise ValueError("config.skip_nonfinite_updates is not supported with replicas (grad_sync): the verdict of a half step must "
+                         "exist before any of its updates is applied, which the deferred and bucketed discriminator update of the "
+                         "data-parallel schedule does not allow")
     if grad_sync is not None and config.get("batch_norm_group_size", -1) > 0:
         grad_sync.require_groups(generator(train=True).bn_groups)
     parts = split_input_dict(batch, n)
@@ -233,10 +240,18 @@ class GraphedTrainStep:
                                             additional_data or {}, grad_sync=grad_sync,
                                             **({"d_aug_host": aug_host} if aug_host is not None else {}))
             new_state = xmc_gan._flush(new_state)
-            bs.flat.copy_(new_state.generator_state["batch_stats"].flat)
-            sn.flat.copy_(new_state.discriminator_state["spectral_norm_stats"].flat)
+            guard = getattr(new_state, "guard", None)
+            if guard is None:
+                bs.flat.copy_(new_state.generator_state["batch_stats"].flat)
+                sn.flat.copy_(new_state.discriminator_state["spectral_norm_stats"].flat)
+            else:
+                # config.skip_nonfinite_updates: every half step committed its statistics and u0 into the persistent flat buffers
+                # itself (xmc_commit_if, under its verdict: the unconditional copies would undo a skip) -- nothing is left to copy
+                # (``commit`` returns at once for a buffer onto itself)
+                guard.commit(ops, bs.flat, new_state.generator_state["batch_stats"].flat)
+                guard.commit(ops, sn.flat, new_state.discriminator_state["spectral_norm_stats"].flat)
             if accumulator is not None:                  # the step's metrics are summed on the device: still one graph launch
-                accumulator.add(metrics)
+                accumulator.add(metrics, verdict=guard.verdict if guard is not None else None)
         # capture executed nothing: undo the host-side mirrors the Python code advanced, keep what a replay must add
         self._d_steps, self._g_steps = da.opt_step - before[1], ga.opt_step - before[0]
         self._steps = int(new_state.step) - before[2]
@@ -431,10 +446,18 @@ class MetricAccumulator:
         self.sums = torch.zeros((len(self.keys),), dtype=torch.float64, device=device)
         self.info = torch.zeros((2,), dtype=torch.int32, device=device)         # [calls, 1-based first call with a non-finite value]
 
-    def add(self, metrics):
+    def add(self, metrics, verdict=None):
+        """``verdict`` (config.skip_nonfinite_updates: the int32[4] of the train_g_d that produced ``metrics``, device memory): a
+        skipped half step adds nothing and is not counted -- decided on the device (``xmc_metrics_accum_if``)"""
         vals = [torch.as_tensor(metrics[k]).detach().reshape(-1) for k in self.keys]
         if self.ops is not None:
-            self.ops.metrics_accum([v if v.dtype == torch.float32 else v.float() for v in vals], self.sums, self.info)
+            vals = [v if v.dtype == torch.float32 else v.float() for v in vals]
+            if verdict is not None:
+                self.ops.metrics_accum_if(vals, self.sums, self.info, verdict)
+            else:
+                self.ops.metrics_accum(vals, self.sums, self.info)
+            return
+        if verdict is not None and int(verdict[0]) != 0:
             return
         v = torch.cat([t.to(self.sums.device, torch.float32) for t in vals])
         self.sums += v.double()
@@ -589,6 +612,9 @@ def train(config, workdir, test_mode=False, *, datasets=None):
     from .libml import diff_augment
     aug_policy = config.get("diff_augment", "")      # differentiable augmentation of D's inputs: a plan per step, like z
     clip_guidance = additional_data.get("clip_guidance") if gan_model is xmc_gan else None      # config.clip_guidance_weight > 0
+    from .libml import nonfinite_guard
+    guard = state.guard if nonfinite_guard.enabled(config) else None      # config.skip_nonfinite_updates: the skip counters
+    skipped_before = guard.read()["skipped"] if guard is not None else 0
     for step in range(initial_step, num_train_steps + 1):
         is_last_step = step == num_train_steps
         item = next(train_iter)
@@ -610,7 +636,7 @@ def train(config, workdir, test_mode=False, *, datasets=None):
         if graphed is None:
             state, metrics = train_step(fold_in(streams["train"], step), state, batch, gan_model, generator, discriminator, config,
                                         additional_data, grad_sync=grad_sync)
-            accumulator.add(metrics)
+            accumulator.add(metrics, verdict=guard.verdict if guard is not None else None)
             if use_graph and not is_last_step:
                 graphed = GraphedTrainStep(state, batch, gan_model, generator, discriminator, config, additional_data,
                                            grad_sync=grad_sync, accumulator=accumulator)
@@ -630,9 +656,26 @@ def train(config, workdir, test_mode=False, *, datasets=None):
                          if bad else "; no gradient held a non-finite value")
             raise FloatingPointError(f"train: a training metric was not finite at step {window_start + first_bad - 1}; "
                                      f"no checkpoint of that state is written (the newest one is {rotation.latest()}){where}")
+        skips = guard.read() if guard is not None else None       # read together with the accumulator: one synchronisation
+        if skips is not None and skips["longest"] >= nonfinite_guard.max_consecutive(config):
+            where = ""
+            if statistics is not None:
+                bad = statistics.read()["first_bad"]
+                where = (f"; the first gradient that held a non-finite value was {bad[1]} at step {window_start + bad[0] - 1}"
+                         if bad else "; no gradient held a non-finite value")
+            raise FloatingPointError(f"train: {skips['longest']} consecutive half steps were skipped for non-finite values "
+                                     f"(config.nonfinite_max_consecutive = {nonfinite_guard.max_consecutive(config)}) by step {step}: "
+                                     f"the parameters or the data are bad and skipping cannot help; no checkpoint of that state is "
+                                     f"written (the newest one is {rotation.latest()}){where}")
         state = xmc_gan._flush(state)
         if write_scalars:
-            scalars = {k: sums[k] / count for k in accumulator.keys}
+            # (a window whose every step was skipped has no metric to average: NaN, as 0 / 0 says)
+            scalars = {k: sums[k] / count if count else float("nan") for k in accumulator.keys}
+            if skips is not None:
+                scalars["guard/skipped_half_steps"] = skips["skipped"] - skipped_before
+                scalars["guard/longest_run"] = skips["longest"]
+                skipped_before = skips["skipped"]
+                guard.reset_longest()
             if statistics is not None:               # this replica's statistics (not averaged over replicas): window means
                 window = statistics.read()
                 if writes:
@@ -648,6 +691,9 @@ def train(config, workdir, test_mode=False, *, datasets=None):
                 grids = generate_batch(fold_in(streams["sample_batch"], step), state, visualize, generator, config)
                 write_image_grids(os.path.join(workdir, "images"), step, grids)
         if write_checkpoint and writes:
+            if guard is not None:                    # Adam's t on the host = the number of APPLIED updates (the device's counter)
+                state.g_optimizer.arena.sync_opt_step()
+                state.d_optimizer.arena.sync_opt_step()
             rotation.save(state)
     if writes:
         manager.mark_training_done()

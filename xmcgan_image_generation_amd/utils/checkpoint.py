@@ -100,12 +100,18 @@ def to_state_dict(state) -> Dict[str, Any]:
     """TrainState -> the nested dict ``flax.serialization.to_state_dict`` produces for the reference's TrainState."""
     if getattr(state, "pending", None) is not None:
         raise ValueError("a deferred discriminator update is pending; checkpoint after train_step returns")
-    return {"step": int(state.step),
-            "g_optimizer": _opt_dict(state.g_optimizer),
-            "d_optimizer": _opt_dict(state.d_optimizer),
-            "generator_state": _np_tree(state.generator_state),
-            "discriminator_state": _np_tree(state.discriminator_state),
-            "ema_params": _np_tree(state.g_optimizer.arena.tree(state.ema_buffer))}
+    if getattr(state, "guard", None) is not None:    # config.skip_nonfinite_updates: the host mirrors of Adam's t may run ahead
+        state.g_optimizer.arena.sync_opt_step()
+        state.d_optimizer.arena.sync_opt_step()
+    out = {"step": int(state.step),
+           "g_optimizer": _opt_dict(state.g_optimizer),
+           "d_optimizer": _opt_dict(state.d_optimizer),
+           "generator_state": _np_tree(state.generator_state),
+           "discriminator_state": _np_tree(state.discriminator_state),
+           "ema_params": _np_tree(state.g_optimizer.arena.tree(state.ema_buffer))}
+    if getattr(state, "guard", None) is not None:    # config.skip_nonfinite_updates (not in the reference): the skip counters
+        out["nonfinite_guard"] = state.guard.state_dict()
+    return out
 
 
 def _load_opt(opt, d):
@@ -131,6 +137,8 @@ def from_state_dict(state, d: Dict[str, Any]):
     _load_opt(state.d_optimizer, d["d_optimizer"])
     state.g_optimizer.arena.load_flax(d["ema_params"], state.ema_buffer)
     ops = state.g_optimizer.arena.ops
+    if getattr(state, "guard", None) is not None and "nonfinite_guard" in d:
+        state.guard.load_state_dict(d["nonfinite_guard"])
     return state.replace(step=int(np.asarray(d["step"])),
                          generator_state={k: xmc_net._tree_to_dev(ops, v) for k, v in d["generator_state"].items()},
                          discriminator_state={k: xmc_net._tree_to_dev(ops, v) for k, v in d["discriminator_state"].items()},

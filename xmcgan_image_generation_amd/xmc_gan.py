@@ -25,6 +25,7 @@ import torch
 from .libml import attention_lib as attn_lib
 from .libml import diff_augment
 from .libml import losses
+from .libml import nonfinite_guard
 from .nets import xmc_net
 from .utils import pretrained_model_utils
 
@@ -393,17 +394,72 @@ def _forward(rng, config, state, batch, g, d, need_g_tape, image_model=None, aft
     return state, out, dld, dlg, g_tape, d_tape, new_g_stats, new_sn, pre, cpre
 
 
-def _apply_adam(ops, opt, config, lr, grad_scale, ema=None, fix_args=None, net=None, stats=None):
+def _guarded(state, config, ops, g, d, grad_sync):
+    """config.skip_nonfinite_updates -> (state, its ``NonfiniteGuard``) with G's running statistics and D's u0 as FlatTrees: the
+    half step commits into those flat buffers (``xmc_commit_if``) instead of returning new trees.  (state, None) with the switch off."""
+    if not nonfinite_guard.enabled(config):
+        return state, None
+    if grad_sync is not None:
+        raise ValueError("config.skip_nonfinite_updates is not supported with replicas (grad_sync): the deferred and bucketed "
+                         "discriminator update applies gradients before a verdict over the whole half step can exist")
+    new = {}
+    if getattr(state, "guard", None) is None:
+        new["guard"] = nonfinite_guard.NonfiniteGuard(ops.device)
+    bs, sn = state.generator_state["batch_stats"], state.discriminator_state["spectral_norm_stats"]
+    if getattr(bs, "flat", None) is None:
+        new["generator_state"] = {"batch_stats": g.flat_batch_stats(state.g_optimizer.target, bs)}
+    if getattr(sn, "flat", None) is None:
+        new["discriminator_state"] = {"spectral_norm_stats": d.flat_sn_stats(state.d_optimizer.target, sn)}
+    state = state.replace(**new) if new else state
+    return state, state.guard
+
+
+def _sn_padding(d, u_new):
+    """indices of the alignment padding between the u slices of D's spectral bank (never written by the power iteration)"""
+    pad = getattr(d, "_u_pad", None)
+    if pad is None:
+        idx, at = [], 0
+        for e in sorted(d.bank["entries"], key=lambda e: e["u_off"]):
+            idx += range(at, e["u_off"])
+            at = e["u_off"] + e["nu"]
+        idx += range(at, u_new.numel())
+        pad = d._u_pad = torch.tensor(idx, dtype=torch.long, device=u_new.device)
+    return pad
+
+
+def _judge(ops, guard, d, segments, u_new):
+    """the half step's verdict, on the stream where all its gradient producers have joined, in front of the first optimiser launch:
+    one scan of everything it is about to commit (``segments``: the gradient arena(s), the new u0 ``u_new``, in train_g_d the new
+    BatchNorm running statistics).  -> verdict (int32[4], device)"""
+    pad = _sn_padding(d, u_new)
+    if pad.numel():
+        u_new.index_fill_(0, pad, 0.0)       # (uninitialised bytes between the slices must not read as a NaN)
+    if hasattr(ops, "join_wgrad"):
+        ops.join_wgrad()
+    return guard.judge(ops, segments)
+
+
+def _apply_adam(ops, opt, config, lr, grad_scale, ema=None, fix_args=None, net=None, stats=None, verdict=None, fresh_u=None):
     """flax.optim.Adam.apply_gradient (+ EMA).  ``fix_args`` (Discriminator.sn_fix_args()): the gradient through sigma of the
     spectrally-normalised weights rides in the optimiser kernel -- its scalar <G, W> is formed HERE, on the gradient the
     update consumes (after the replicas' exchange: the term is linear in G, and u, v, sigma are identical on every replica).
     ``net`` (the Generator / Discriminator that owns the arena; round 5, ops.fuse_prep): the update of its batched-preparation
     weights also EMITS their prepared copies for the next forward pass (xmc_adam_wprep_tiles).
     ``stats`` = (TrainStatistics, "d" | "g") (train_g_d's own updates only): the per-tensor sums of squares of the gradient this
-    update consumes and of the parameters it is about to change, in front of it on this update's stream."""
+    update consumes and of the parameters it is about to change, in front of it on this update's stream.
+    ``verdict`` (config.skip_nonfinite_updates): the half step's verdict in device memory -- the guarded forms of the kernels
+    read it and leave parameters, moments, EMA, Adam's t and the prepared copies untouched when it is bad (the host mirror
+    ``opt_step`` then runs ahead until ``ParamArena.sync_opt_step``).  ``fresh_u``: the persistent u0 buffer the half step
+    commits its new u into (what the next power iteration will read) -- the prepared copies are fresh with respect to IT."""
     a = opt.arena
     if stats is not None:
         stats[0].leaf_pass(ops, stats[1], a, grad_scale)
+    guard_kw = {"verdict": verdict} if verdict is not None else {}
+    if verdict is not None and a.step_state is None:
+        # no device-side step counter (an operator table without adam_ema_dev): this path is eager by construction, Adam's t is the
+        # host's -- read the verdict here, so that t stays the number of applied updates
+        if int(verdict[0]) != 0:
+            return
     a.note_steps(1)
     decay = config.polyak_decay if ema is not None else 0.0
     if getattr(a, "first_write", False):
@@ -420,20 +476,20 @@ def _apply_adam(ops, opt, config, lr, grad_scale, ema=None, fix_args=None, net=N
         zero = not getattr(a, "first_write", False)
         a.grads_clean = ops.adam_ema_dev_sn(a.params, a.grads, a.m, a.v, ema, a.step_state, lr=lr, beta1=config.beta1,
                                             beta2=config.beta2, grad_scale=grad_scale, ema_decay=decay, fix=fix, zero_grads=zero,
-                                            **({"skip_map": prep["skip_map"]} if prep is not None and fix is None else {}))
+                                            **({"skip_map": prep["skip_map"]} if prep is not None and fix is None else {}), **guard_kw)
         if prep is not None:                 # ... and the tensors that kernel skipped: update + prepared copies in one pass
             ops.adam_wprep(prep["wp"], prep["out"], a.params, a.grads, a.m, a.v, ema, a.step_state, lr=lr, beta1=config.beta1,
                            beta2=config.beta2, grad_scale=grad_scale, ema_decay=decay, zero_grads=zero,
-                           fix=(kvec, fix_args[2], fix_args[3], fix_args[4]) if fix_args is not None else None)
+                           fix=(kvec, fix_args[2], fix_args[3], fix_args[4]) if fix_args is not None else None, **guard_kw)
     elif a.step_state is not None:          # device-side step counter (hipGraph-replayable)
         ops.adam_ema_dev(a.params, a.grads, a.m, a.v, ema, a.step_state, lr=lr, beta1=config.beta1,
-                         beta2=config.beta2, grad_scale=grad_scale, ema_decay=decay)
+                         beta2=config.beta2, grad_scale=grad_scale, ema_decay=decay, **guard_kw)
     else:
         ops.adam_ema(a.params, a.grads, a.m, a.v, ema, lr=lr, beta1=config.beta1, beta2=config.beta2,
                      step=a.opt_step, grad_scale=grad_scale, ema_decay=decay)
     a.version += 1
     if prep is not None:
-        net.note_adam_prepared(a, fix_args[3] if fix_args is not None else None)
+        net.note_adam_prepared(a, (fresh_u if fresh_u is not None else fix_args[3]) if fix_args is not None else None)
 
 
 def _fix_args(d):
@@ -483,6 +539,7 @@ def train_d(rng, state, batch, generator, discriminator, config, grad_sync=None,
     ops = g.ops
     if hasattr(ops, "begin_pool"):
         ops.begin_pool()
+    state, guard = _guarded(state, config, ops, g, d, grad_sync)
     d_arena = state.d_optimizer.arena
     deferred_in = getattr(state, "pending", None) is not None
     if not deferred_in:
@@ -535,6 +592,15 @@ def train_d(rng, state, batch, generator, discriminator, config, grad_sync=None,
         grad_sync.wait("d")
     if do_prefetch and prefetched is None:
         prefetch()                           # (_PREFETCH_AT_ADAM: the side stream forks here, behind the backward pass)
+    if guard is not None:
+        # config.skip_nonfinite_updates: the half step commits D's update and the new u0, or neither
+        u0 = state.discriminator_state["spectral_norm_stats"].flat
+        # (G's new running statistics are discarded as always, but they are scanned: a NaN the generator's forward pass met
+        # shows in its batch statistics even where a max(x, 0) further on turned it into a finite, meaningless image)
+        verdict = _judge(ops, guard, d, [d_arena.grads, new_sn.flat, _new_g_stats.flat], new_sn.flat)
+        _apply_adam(ops, state.d_optimizer, config, config.d_lr, scale, fix_args=fix_args, net=d, verdict=verdict, fresh_u=u0)
+        guard.commit(ops, u0, new_sn.flat)
+        return state.replace(prefetched_g=prefetched)
     _apply_adam(ops, state.d_optimizer, config, config.d_lr, scale, fix_args=fix_args, net=d)
     # G's new batch_stats are discarded (xmc_gan.py:231); D's new u0 are kept (:253-255)
     return state.replace(discriminator_state={"spectral_norm_stats": new_sn}, prefetched_g=prefetched)
@@ -546,6 +612,7 @@ def train_g_d(rng, state, batch, generator, discriminator, config, additional_da
     ops = g.ops
     if hasattr(ops, "begin_pool"):
         ops.begin_pool()
+    state, guard = _guarded(state, config, ops, g, d, grad_sync)
     d_arena, g_arena = state.d_optimizer.arena, state.g_optimizer.arena
     if getattr(state, "pending", None) is None:
         d_arena.zero_grads()                 # (with a deferred D update the arena is still being exchanged: _forward)
@@ -574,6 +641,9 @@ def train_g_d(rng, state, batch, generator, discriminator, config, additional_da
             ops.add_into(dimg, pull())
         return dimg
     excl = grad_sync is not None and getattr(grad_sync, "exclusive", False)
+    # D's update beside G's backward pass -- not under config.skip_nonfinite_updates: one verdict covers the half step, and it
+    # needs G's gradients, so both updates are issued behind the join
+    early_adam_d = grad_sync is None and _EARLY_ADAM_D and guard is None
     if _ovl(ops, _OVERLAP_BWD) and (grad_sync is None or _DP_OVERLAP or excl) and hasattr(ops, "side"):
         dlg_f = dlg[b:].contiguous()
         on_ready = None
@@ -589,7 +659,7 @@ def train_g_d(rng, state, batch, generator, discriminator, config, additional_da
             ops.join_side(_leaf_tensors(pre[2]) + [pre[1]])                  # the ResNet forward ran on the side stream (_forward)
             with ops.side():
                 dimg = _augment_pullback(ops, d_tape, d.backward_g(d_tape, dlg_f))   # pullback (0, 1), D part
-                if grad_sync is None and _EARLY_ADAM_D:
+                if early_adam_d:
                     d_part_done = ops.record_event()
             if _RESNET_BWD_MAIN == 2:                                        # A/B: on a THIRD stream, beside D's backward pass as well
                 with ops.side(2):
@@ -619,7 +689,7 @@ def train_g_d(rng, state, batch, generator, discriminator, config, additional_da
         else:
             with ops.side():                                   # (stream graph main -> {side, wgrad}: no cross edges)
                 dimg = image_pullback(dlg_f)                                 # pullback (0, 1), D (+ ResNet) part
-                if grad_sync is None and _EARLY_ADAM_D and hasattr(ops, "record_event"):
+                if early_adam_d and hasattr(ops, "record_event"):
                     d_part_done = ops.record_event()                         # the g-stream is done with D's parameters here
                 g.backward(g_tape, dimg, on_ready)                           #                  G part
         ops.wgrad_async = async_wg
@@ -647,7 +717,7 @@ def train_g_d(rng, state, batch, generator, discriminator, config, additional_da
             grad_sync.wait("d")
             grad_sync.wait("g")
         return _finish_g_d(ops, state, config, out, c_pre, new_g_stats, new_sn, d_scale, g_scale, grad_sync, _fix_args(d),
-                           d_updated=d_updated, nets=(g, d), stats=stats, c_clip=c_clip)
+                           d_updated=d_updated, nets=(g, d), stats=stats, c_clip=c_clip, guard=guard)
     keep_async = getattr(ops, "wgrad_async", False)
     if grad_sync is not None and hasattr(ops, "wgrad_async"):
         ops.wgrad_async = True               # data-parallel schedule: weight gradients beside the dgrad chain
@@ -675,29 +745,41 @@ def train_g_d(rng, state, batch, generator, discriminator, config, additional_da
         grad_sync.wait("d")
         grad_sync.wait("g")
     return _finish_g_d(ops, state, config, out, c_pre, new_g_stats, new_sn, d_scale, g_scale, grad_sync, _fix_args(d), nets=(g, d),
-                       stats=stats, c_clip=c_clip)
+                       stats=stats, c_clip=c_clip, guard=guard)
 
 
 def _finish_g_d(ops, state, config, out, c_pre, new_g_stats, new_sn, d_scale, g_scale, grad_sync, fix_args=None, d_updated=False,
-                nets=(None, None), stats=None, c_clip=None):
+                nets=(None, None), stats=None, c_clip=None, guard=None):
     """Optimiser updates, EMA, new state and metrics of train_g_d (xmc_gan.py:170-190).  ``d_updated``: the caller already
     applied D's update (beside the generator's backward pass).  ``stats``: the step's ``TrainStatistics`` or None.  ``c_clip``:
-    the unweighted CLIP image-text term (config.clip_guidance_weight) or None."""
+    the unweighted CLIP image-text term (config.clip_guidance_weight) or None.  ``guard`` (config.skip_nonfinite_updates): ONE verdict
+    over both gradient arenas, the new u0 and the new running statistics; both updates and both state buffers commit, or nothing."""
     if grad_sync is not None:
         grad_sync.wait("d")
+    kw_d, kw_g = {}, {}
+    if guard is not None:
+        bs, u0 = state.generator_state["batch_stats"].flat, state.discriminator_state["spectral_norm_stats"].flat
+        verdict = _judge(ops, guard, nets[1], [state.d_optimizer.arena.grads, state.g_optimizer.arena.grads, new_sn.flat,
+                                               new_g_stats.flat], new_sn.flat)
+        kw_d, kw_g = dict(verdict=verdict, fresh_u=u0), dict(verdict=verdict)
     if not d_updated:
         _apply_adam(ops, state.d_optimizer, config, config.d_lr, d_scale, fix_args=fix_args, net=nets[1],
-                    stats=(stats, "d") if stats is not None else None)
+                    stats=(stats, "d") if stats is not None else None, **kw_d)
     if grad_sync is not None:
         grad_sync.wait("g")
     ema = state.ema_buffer if config.get("ema", True) else None
     _apply_adam(ops, state.g_optimizer, config, config.g_lr, g_scale, ema, net=nets[0],      # + EMA, xmc_gan.py:174-177
-                stats=(stats, "g") if stats is not None else None)
+                stats=(stats, "g") if stats is not None else None, **kw_g)
     if stats is not None:
         stats.finish(ops)
-    new_state = state.replace(step=state.step + 1,
-                              generator_state={"batch_stats": new_g_stats},
-                              discriminator_state={"spectral_norm_stats": new_sn})
+    if guard is not None:                    # the state keeps its flat buffers; the batch was consumed: state.step advances
+        guard.commit(ops, bs, new_g_stats.flat)
+        guard.commit(ops, u0, new_sn.flat)
+        new_state = state.replace(step=state.step + 1)
+    else:
+        new_state = state.replace(step=state.step + 1,
+                                  generator_state={"batch_stats": new_g_stats},
+                                  discriminator_state={"spectral_norm_stats": new_sn})
     metrics = dict(out)
     if c_pre is not None:                                                    # xmc_gan.py:149-156
         metrics["c_loss_g_pretrained"] = c_pre[0]
