@@ -16,6 +16,7 @@ import torch  # noqa: F401  (ordering matters)
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libxmcgan_hip.so")
 PROBE_LIB_PATH = os.path.join(_HERE, "libxmc_probe.so")
+CODEC_LIB_PATH = os.path.join(_HERE, "libxmc_codec.so")
 
 XMC_F32, XMC_BF16 = 0, 1
 ABI_VERSION = 36
@@ -245,6 +246,19 @@ PROBE_SIGNATURES = {
     "xmc_class_neighbour": [_I, _I, _I, _P, _L, _P, _P],
 }
 
+# image codec kernels of the dataset builder: include/xmc_codec.h, libxmc_codec.so (csrc_codec/) -- outside the product ABI
+CODEC_ABI_VERSION = 1
+CODEC_DESC_WORDS = 16                 # XMC_CODEC_DESC_WORDS
+CODEC_SIGNATURES = {
+    "xmc_codec_abi_version": [],
+    "xmc_jpeg_plane_bytes": [_I, _I, _I, _I, _I],
+    "xmc_jpeg_decode_workspace_bytes": [_P, _I],
+    "xmc_jpeg_decode_batch": [_P, _L, _P, _L, _P, _I, _P, _L, _P, _L, _P],
+    "xmc_png_filter_workspace_bytes": [_P, _I],
+    "xmc_png_filter_batch": [_P, _L, _P, _I, _P, _L, _P, _L, _P],
+}
+_CODEC_INT64_RETURNS = ("xmc_jpeg_plane_bytes", "xmc_jpeg_decode_workspace_bytes", "xmc_png_filter_workspace_bytes")
+
 _INT64_RETURNS = ("xmc_conv2d_mx8_workspace_bytes", "xmc_conv2d_mx8_phase_in_workspace_bytes", "xmc_conv2d_workspace_bytes", "xmc_bn_stats_ws_floats", "xmc_cbn_bwd_sums_ws_floats",
                   "xmc_conv2d_wgrad_workspace_bytes", "xmc_reduce_mid_ws_floats", "xmc_gemm_ws_floats", "xmc_segment_sumsq_ws_bytes", "xmc_sample_metrics_ws_bytes",
                   "xmc_diffaug_workspace_bytes", "xmc_nonfinite_verdict_workspace_bytes")
@@ -294,6 +308,30 @@ def load_probe():
         fn.argtypes = argtypes
         fn.restype = C.c_int
     _probe = lib
+    return lib
+
+
+_codec = None
+
+
+def load_codec():
+    """The image codec kernels (libml/codec.py, preprocess_data.py): a separate library, never needed by a training step"""
+    global _codec
+    if _codec is not None:
+        return _codec
+    if not os.path.exists(CODEC_LIB_PATH):
+        raise XmcError(f"{CODEC_LIB_PATH} not found: build it with `make -C xmcgan_image_generation_amd/csrc_codec`")
+    lib = C.CDLL(CODEC_LIB_PATH)
+    for name, argtypes in CODEC_SIGNATURES.items():
+        try:
+            fn = getattr(lib, name)
+        except AttributeError as e:
+            raise XmcError(f"{CODEC_LIB_PATH} does not export {name}; rebuild the library") from e
+        fn.argtypes = argtypes
+        fn.restype = C.c_int64 if name in _CODEC_INT64_RETURNS else C.c_int
+    if lib.xmc_codec_abi_version() != CODEC_ABI_VERSION:
+        raise XmcError("libxmc_codec.so ABI version mismatch; rebuild the library")
+    _codec = lib
     return lib
 
 

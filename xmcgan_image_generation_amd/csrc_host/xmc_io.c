@@ -682,4 +682,4 @@ int xmc_resize_bilinear_rgb(const uint8_t* src, int32_t hs, int32_t ws, float* d
     return 0;
 }
 
-int xmc_io_abi_version(void) { return 4; }
+int xmc_io_abi_version(void) { return 5; }

@@ -1,5 +1,6 @@
-"""ctypes binding of ``libxmc_io.so`` (csrc_host/xmc_io.c): CRC-32C, PNG un-filter, bilinear resize.  Host-side
-input-pipeline helpers only -- nothing here touches the GPU or the training step."""
+"""ctypes binding of ``libxmc_io.so`` (csrc_host/): CRC-32C, PNG un-filter, inflate, bilinear resize, and the JPEG entropy
+decoder (xmc_jpeg.c; its Python face is ``libml/jpeg.py``).  Host-side helpers only -- nothing here touches the GPU or the
+training step."""
 from __future__ import annotations
 
 import ctypes as C
@@ -38,7 +39,11 @@ def load():
         lib.xmc_inflate_zlib.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64]
         lib.xmc_inflate_zlib.restype = C.c_int
         lib.xmc_inflate_out_slack.restype = C.c_int32
-        assert lib.xmc_io_abi_version() == 4
+        lib.xmc_jpeg_info.argtypes = [C.c_void_p, C.c_int64, C.c_void_p]
+        lib.xmc_jpeg_info.restype = C.c_int
+        lib.xmc_jpeg_coefficients.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64]
+        lib.xmc_jpeg_coefficients.restype = C.c_int
+        assert lib.xmc_io_abi_version() == 5
         _lib = lib
     return _lib
 

@@ -95,3 +95,43 @@ def encode_rgb(img: np.ndarray, filter_types=None) -> bytes:
         return struct.pack(">I", len(body)) + typ + body + struct.pack(">I", zlib.crc32(typ + body) & 0xffffffff)
     return _SIG + chunk(b"IHDR", struct.pack(">IIBBBBB", w, h, 8, 2, 0, 0, 0)) + \
         chunk(b"IDAT", zlib.compress(bytes(raw), 6)) + chunk(b"IEND", b"")
+
+
+def _chunk(typ: bytes, body: bytes) -> bytes:
+    return struct.pack(">I", len(body)) + typ + body + struct.pack(">I", zlib.crc32(typ + body) & 0xffffffff)
+
+
+def filter_rows_np(img: np.ndarray):
+    """uint8 (H, W, 3) -> (the filtered scanlines with their filter bytes, uint8 (H * (1 + 3 W),); the filter ids, uint8 (H,)).
+
+    The specification of ``xmc_png_filter_batch`` (``csrc_codec/png_filter.hip``).  Per row every filter of the PNG standard
+    is tried -- 0 None, 1 Sub, 2 Up, 3 Average, 4 Paeth, with bytes left of the row and above the image read as 0 -- and
+    the one whose filtered bytes, read as SIGNED, have the smallest sum of absolute values is kept; ties go to the lowest
+    id.  The result is the stream ``zlib.compress`` takes (``encode_filtered``)."""
+    img = np.ascontiguousarray(img, np.uint8)
+    h, w, c = img.shape
+    assert c == 3
+    rows = img.reshape(h, w * 3).astype(np.int64)
+    up = np.concatenate([np.zeros((1, w * 3), np.int64), rows[:-1]])
+    left = np.concatenate([np.zeros((h, 3), np.int64), rows[:, :-3]], axis=1)
+    ul = np.concatenate([np.zeros((h, 3), np.int64), up[:, :-3]], axis=1)
+    p = left + up - ul
+    pa, pb, pc = np.abs(p - left), np.abs(p - up), np.abs(p - ul)
+    paeth = np.where((pa <= pb) & (pa <= pc), left, np.where(pb <= pc, up, ul))
+    cand = np.stack([rows, rows - left, rows - up, rows - ((left + up) >> 1), rows - paeth]) & 0xff        # (5, H, 3W)
+    cost = np.where(cand >= 128, 256 - cand, cand).sum(axis=2)                                               # (5, H)
+    ids = cost.argmin(axis=0)                                                                                # first minimum
+    out = np.empty((h, 1 + w * 3), np.uint8)
+    out[:, 0] = ids
+    out[:, 1:] = cand[ids, np.arange(h)]
+    return out.reshape(-1), ids.astype(np.uint8)
+
+
+def encode_filtered(stream, h: int, w: int, level: int = 6) -> bytes:
+    """filtered scanlines of an 8-bit RGB image (``filter_rows_np`` or the device filter) -> PNG bytes"""
+    if not isinstance(stream, (bytes, bytearray)):
+        stream = np.ascontiguousarray(stream, np.uint8).tobytes()
+    if len(stream) != h * (1 + 3 * w):
+        raise ValueError(f"PNG: {len(stream)} filtered bytes for {w} x {h} RGB pixels")
+    return _SIG + _chunk(b"IHDR", struct.pack(">IIBBBBB", w, h, 8, 2, 0, 0, 0)) + \
+        _chunk(b"IDAT", zlib.compress(stream, level)) + _chunk(b"IEND", b"")
