@@ -1062,6 +1062,27 @@ int xmc_adam_wprep_tiles_guarded(const void* table, int32_t n, int32_t blocks, f
                                  const int32_t* verdict, void* stream);
 int xmc_metrics_accum_if(const float* const* vals, int32_t n, double* sums, int32_t* info, const int32_t* verdict, void* stream);
 
+/* ---- adaptive discriminator augmentation (config.ada_target; libml/ada.py is the specification; csrc/ada.hip) ----
+ * XMC_ABI_VERSION stays 36: this section only ADDS entry points, no existing signature or structure changes, and a library built
+ * before it fails loudly at symbol resolution when it is loaded (every declared symbol must resolve).
+ * `state` is the controller's persistent float64[8] in device memory, 8-byte aligned (the caller zeroes it once):
+ *     [0] p   [1] sign_sum   [2] count   [3] ticks   [4] last_r   [5] adjustments   [6], [7] not touched
+ *  - xmc_ada_gate: rows[2b][8] from plan[b][2][8] and the uniforms u[b][2][5] (index 1: real / generated), real rows first (the
+ *    layout xmc_diffaug_fwd reads).  Part g (brightness, saturation, contrast, translation, cutout: columns {0}, {1}, {2}, {3, 4},
+ *    {5, 6, 7}) of a row keeps the plan's values iff (double)u < state[0], read on the device; otherwise its columns take the
+ *    identity values (0, 1, 1, 0, 0, 0, 0, 0).  One thread per row, two 16-byte stores, one writer per element.
+ *    Domain: 1 <= b, 2 b <= 65535; plan and rows 16-byte aligned, u 4-byte aligned.
+ *  - xmc_ada_update: one half step of the controller over logit[0 .. b), the REAL half of D's float32 logit vector (nothing
+ *    behind it is read).  Over the finite logits: sign_sum += #(x > 0) - #(x < 0), count += #finite (+-0 has sign 0); ticks += 1.
+ *    When ticks >= interval: if count > 0, in IEEE double and in this order, r = sign_sum / count, sgn = (r > target) - (r < target),
+ *    p = min(max(p + sgn * (count / images_to_full), 0), p_max), last_r = r, adjustments += 1; in every case sign_sum = count =
+ *    ticks = 0.  One workgroup, no atomics: the counts are integers, so the result is bit-equal to the specification.
+ *    Domain: 1 <= b, 1 <= interval, images_to_full > 0, p_max >= 0, target not NaN.
+ * Anything else returns XMC_EINVAL and launches nothing. */
+int xmc_ada_gate(const float* plan, const float* u, const double* state, float* rows, int32_t b, void* stream);
+int xmc_ada_update(const float* logit, int32_t b, double* state, double target, double images_to_full, int32_t interval,
+                   double p_max, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

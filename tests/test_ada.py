@@ -1,0 +1,345 @@
+"""config.ada_target without a GPU: the gate uniforms, the NumPy specification of the gate and of the controller (libml/ada.py),
+the configuration errors, the switch through ``train_step`` on the CPU operator table (tests/cpu_ops.py has neither ``ada_gate``
+nor ``ada_update``: the controller takes the specification), and the controller's state through a checkpoint."""
+import numpy as np
+import pytest
+import torch
+
+from tests.cpu_ops import CpuOps
+from xmcgan_image_generation_amd import synthetic as syn
+from xmcgan_image_generation_amd import train_utils, xmc_gan
+from xmcgan_image_generation_amd.configs import coco_xmc
+from xmcgan_image_generation_amd.libml import ada as ADA
+from xmcgan_image_generation_amd.libml import diff_augment as DA
+from xmcgan_image_generation_amd.nets import xmc_net
+from xmcgan_image_generation_amd.utils import checkpoint
+
+FULL = "color,translation,cutout"
+IDENT = np.asarray(DA.IDENTITY_ROW, np.float32)
+COLUMNS = ((0,), (1,), (2,), (3, 4), (5, 6, 7))
+
+
+@pytest.fixture(scope="module")
+def cpu_table():
+    xmc_net.set_ops_factory(lambda dtype: CpuOps(dtype))
+    yield
+    xmc_net.set_ops_factory(None)
+
+
+# -------------------------------------------------------------------------------------------------------------- draw_gates
+def test_draw_gates_is_pure_in_range_and_on_the_float32_grid():
+    u = ADA.draw_gates(7, 3, 0, 600)
+    assert u.dtype == np.float32 and u.shape == (600, 2, 5)
+    assert u.tobytes() == ADA.draw_gates(7, 3, 0, 600).tobytes()
+    assert (u >= 0).all() and (u < 1).all()
+    scaled = u.astype(np.float64) * 2.0 ** 24
+    assert np.array_equal(scaled, np.round(scaled))                       # multiples of 2^-24
+    for other in (ADA.draw_gates(8, 3, 0, 600), ADA.draw_gates(7, 4, 0, 600), ADA.draw_gates(7, 3, 1, 600)):
+        assert (u != other).mean() > 0.99
+    assert np.array_equal(u[:4], ADA.draw_gates(7, 3, 0, 600)[:4])
+    assert 0.45 < u.mean() < 0.55 and len(np.unique(u)) > 5900
+
+
+def test_draw_plan_numbers_do_not_move():
+    """the gates come from a SeedSequence of their own: ``draw_plan`` restated here from its docstring gives the same bytes as
+    the module's, before and after a ``draw_gates`` call with the same arguments"""
+    seed, step, rank, n, h, w = 7, 3, 0, 6, 16, 24
+    before = DA.draw_plan(seed, step, rank, n, h, w, FULL).tobytes()
+    ADA.draw_gates(seed, step, rank, n)
+    assert DA.draw_plan(seed, step, rank, n, h, w, FULL).tobytes() == before
+    rng = np.random.default_rng(np.random.SeedSequence([seed, step, rank]))
+    u = rng.random((3, n, 2), dtype=np.float32)
+    want = DA.identity_plan(n)
+    want[..., 0], want[..., 1] = u[0] - np.float32(0.5), u[1] * np.float32(2.0)
+    want[..., 2] = np.minimum(u[2] + np.float32(0.5), np.nextafter(np.float32(1.5), np.float32(0.0)))
+    rh, rw, c = DA.translation_range(h), DA.translation_range(w), DA.cutout_side(h)
+    want[..., 3], want[..., 4] = rng.integers(-rh, rh + 1, (n, 2)), rng.integers(-rw, rw + 1, (n, 2))
+    cy, cx = rng.integers(0, h + 1 - c % 2, (n, 2)), rng.integers(0, w + 1 - c % 2, (n, 2))
+    want[..., 5], want[..., 6], want[..., 7] = cy - c // 2, cx - c // 2, c
+    assert want.tobytes() == before
+    # and the gates are not the plan's colour uniforms under another name
+    assert not np.array_equal(ADA.draw_gates(seed, step, rank, n)[..., 0], u[0])
+
+
+# -------------------------------------------------------------------------------------------------------------------- gate
+def _real_first(plan):
+    return np.ascontiguousarray(np.asarray(plan, np.float32).transpose(1, 0, 2).reshape(-1, 8))
+
+
+def _changed(rows):
+    """bool [2n, 5]: does part g of a row differ from its identity value?"""
+    return np.stack([(rows[:, list(c)] != IDENT[list(c)]).any(axis=1) for c in COLUMNS], axis=1)
+
+
+def test_gate_ends_and_monotonicity():
+    n, h, w = 40, 16, 24
+    plan, u = DA.draw_plan(5, 2, 0, n, h, w, FULL), ADA.draw_gates(5, 2, 0, n)
+    full = _real_first(plan)
+    assert ADA.gate(plan, u, 0.0).tobytes() == _real_first(DA.identity_plan(n)).tobytes()
+    assert ADA.gate(plan, u, 1.0).tobytes() == full.tobytes()
+    assert ADA.gate(plan, u, 0.0).dtype == np.float32 and ADA.gate(plan, u, 0.0).shape == (2 * n, 8)
+    below = lambda p: (u.astype(np.float64) < p).transpose(1, 0, 2).reshape(2 * n, 5)          # noqa: E731
+    prev = np.zeros((2 * n, 5), bool)
+    for p in (0.0, 2.0 ** -24, 0.1, 0.3, 0.5, 0.8, 1.0 - 2.0 ** -53, 1.0):
+        rows = ADA.gate(plan, u, p)
+        now = _changed(rows)
+        assert (now | ~prev).all()                                        # the set of applied parts only grows with p
+        prev = now
+        # every part is the plan's or the identity's, as its own uniform says
+        assert rows.tobytes() == np.where(np.repeat(below(p), [1, 1, 1, 2, 3], axis=1), full, IDENT).tobytes()
+        DA.check_plan(rows, h, w)                                         # a gated plan passes whenever the drawn one does
+    assert np.array_equal(prev, _changed(full)) and prev.mean() > 0.9
+    assert 0.2 < _changed(ADA.gate(plan, u, 0.3)).mean() < 0.4
+
+
+def test_gate_is_strict_and_compares_in_float64():
+    n = 3
+    plan = DA.draw_plan(1, 1, 0, n, 16, 16, FULL)
+    p32 = np.float32(0.3)                                                 # a float32-representable p, as a double
+    u = np.full((n, 2, 5), p32, np.float32)
+    u[1] = 0.0
+    u[2] = np.nextafter(p32, np.float32(0.0))
+    rows = ADA.gate(plan, u, float(p32))
+    full = _real_first(plan)
+    for sample, applied in ((0, False), (1, True), (2, True)):            # a tie is not applied; 0 and the float below p are
+        for half in (0, 1):
+            r = half * n + sample
+            assert np.array_equal(rows[r], full[r] if applied else IDENT), (sample, half)
+    # 0.3 (a double with no float32 twin) lies BELOW float32(0.3): u = float32(0.3) is not applied, which a float32 compare would miss
+    assert float(p32) > 0.3 and np.float32(0.3) == p32
+    assert np.array_equal(ADA.gate(plan, u, 0.3)[0], IDENT) and np.array_equal(ADA.gate(plan, u, 0.3)[2], full[2])
+    # u = 0 is applied for any p > 0, the smallest double included, and never for p = 0
+    zero = np.zeros((n, 2, 5), np.float32)
+    assert ADA.gate(plan, zero, 5e-324).tobytes() == full.tobytes()
+    assert ADA.gate(plan, zero, 0.0).tobytes() == _real_first(DA.identity_plan(n)).tobytes()
+    with pytest.raises(ValueError):
+        ADA.gate(plan, zero[:, :1], 0.5)
+
+
+def test_controller_gate_in_torch_equals_the_specification():
+    n = 9
+    plan, u = DA.draw_plan(2, 1, 0, n, 16, 16, FULL), ADA.draw_gates(2, 1, 0, n)
+    u[0, 0, :] = np.float32(0.5)
+    ctl = ADA.AdaController("cpu")
+    for p in (0.0, 0.3, 0.5, 1.0):
+        ctl.state[0] = p
+        got = ctl.gate(object(), torch.from_numpy(plan), torch.from_numpy(u))
+        assert got.is_contiguous() and got.numpy().tobytes() == ADA.gate(plan, u, p).tobytes()
+
+
+# ------------------------------------------------------------------------------------------------------------------ update
+def _run(logit_sets, target=0.6, full=100.0, interval=4, p_max=ADA.P_MAX, state=None):
+    s = ADA.initial_state() if state is None else np.asarray(state, np.float64)
+    out = []
+    for x in logit_sets:
+        s = ADA.update(s, np.asarray(x, np.float32), target, full, interval, p_max)
+        out.append(s.copy())
+    return out
+
+
+def test_update_all_positive_raises_p_by_count_over_images_to_full_until_p_max():
+    hist = _run([np.ones(5)] * 40, full=100.0, interval=4)
+    step = 20.0 / 100.0
+    for i, s in enumerate(hist):
+        done = (i + 1) // 4
+        assert s[ADA.P] == min(done * step, ADA.P_MAX) and s[ADA.ADJUSTMENTS] == done
+        assert s[ADA.TICKS] == (i + 1) % 4 and s[ADA.COUNT] == 5 * ((i + 1) % 4) == s[ADA.SIGN_SUM]
+        assert s[ADA.LAST_R] == (1.0 if done else 0.0) and s[6] == 0 and s[7] == 0
+    assert hist[-1][ADA.P] == ADA.P_MAX == 0.8
+    assert _run([np.ones(5)] * 40, full=100.0, p_max=1.0)[-1][ADA.P] == 1.0
+    # exactly count / images_to_full, in double: 3 / 7000 is no short decimal
+    assert _run([np.ones(3)], full=7000.0, interval=1)[0][ADA.P] == 3.0 / 7000.0
+
+
+def test_update_all_negative_keeps_p_at_zero_and_lowers_a_positive_p():
+    hist = _run([-np.ones(5)] * 8)
+    assert all(s[ADA.P] == 0.0 for s in hist) and hist[-1][ADA.ADJUSTMENTS] == 2 and hist[-1][ADA.LAST_R] == -1.0
+    start = ADA.initial_state()
+    start[ADA.P] = 0.5
+    assert _run([-np.ones(5)] * 4, state=start)[-1][ADA.P] == 0.5 - 20.0 / 100.0
+
+
+def test_update_at_the_target_counts_an_adjustment_and_leaves_p():
+    start = ADA.initial_state()
+    start[ADA.P] = 0.25
+    (s,) = _run([[2.0, 0.5, -1.0, 3.0]], target=0.5, interval=1, state=start)         # r = (3 - 1) / 4 = 0.5 exactly
+    assert s[ADA.P] == 0.25 and s[ADA.LAST_R] == 0.5 and s[ADA.ADJUSTMENTS] == 1
+    assert s[ADA.SIGN_SUM] == s[ADA.COUNT] == s[ADA.TICKS] == 0
+
+
+def test_update_skips_non_finite_logits_and_gives_zero_no_sign():
+    x = np.array([np.nan, np.inf, -np.inf, 1.0, -2.0, 3.0, 0.0, -0.0, 1e-45, -1e-45], np.float32)
+    (s,) = _run([x], interval=2)
+    assert s[ADA.COUNT] == 7 and s[ADA.SIGN_SUM] == 1 and s[ADA.TICKS] == 1 and s[ADA.P] == 0 and s[ADA.ADJUSTMENTS] == 0
+    # +-0 alone: counted, sign 0 -> r = 0 < target: p goes down
+    start = ADA.initial_state()
+    start[ADA.P] = 0.5
+    (s,) = _run([np.array([0.0, -0.0], np.float32)], interval=1, full=10.0, state=start)
+    assert s[ADA.LAST_R] == 0.0 and s[ADA.P] == 0.5 - 0.2 and s[ADA.ADJUSTMENTS] == 1
+    # an interval of non-finite logits only: nothing changes but the reset
+    start[ADA.LAST_R], start[ADA.ADJUSTMENTS] = 0.125, 3.0
+    hist = _run([np.array([np.nan, np.inf], np.float32)] * 2, interval=2, state=start)
+    assert hist[0][ADA.TICKS] == 1 and hist[0][ADA.COUNT] == 0
+    want = start.copy()
+    assert hist[1].tobytes() == want.tobytes()
+
+
+# ----------------------------------------------------------------------------------------------------------- configuration
+B = 2
+
+
+def _cfg(policy, **kw):
+    cfg = coco_xmc.get_test_config()
+    cfg.batch_size = B
+    cfg.diff_augment = policy
+    cfg.update(kw)
+    return cfg
+
+
+def test_the_keys_are_absent_from_every_config():
+    for cfg in (coco_xmc.get_config(), coco_xmc.get_test_config()):
+        assert all(k not in cfg for k in ("ada_target", "ada_kimg", "ada_interval"))
+        assert not ADA.enabled(cfg)
+    assert ADA.settings(_cfg(FULL, ada_target=0.6)) == dict(target=0.6, images_to_full=500000.0, interval=4)
+    assert not ADA.enabled(_cfg(FULL, ada_target=0)) and not ADA.enabled(_cfg(FULL, ada_target=0.0))
+
+
+@pytest.mark.parametrize("policy, kw, match", [("", dict(ada_target=0.6), "diff_augment"), (FULL, dict(ada_target=1.0), "ada_target"),
+                                               (FULL, dict(ada_target=1.5), "ada_target"), (FULL, dict(ada_target=-0.1), "ada_target"),
+                                               (FULL, dict(ada_target=0.6, ada_kimg=0), "ada_kimg"),
+                                               (FULL, dict(ada_target=0.6, ada_interval=0), "ada_interval")])
+def test_create_train_state_rejects_bad_settings_before_it_allocates(policy, kw, match):
+    made = []
+    xmc_net.set_ops_factory(lambda dtype: made.append(dtype) or CpuOps(dtype))
+    try:
+        with pytest.raises(ValueError, match=match):
+            train_utils.create_train_state(_cfg(policy, **kw), 0)
+    finally:
+        xmc_net.set_ops_factory(None)
+    assert not made                                   # not even the operator table was built
+
+
+def _fresh(cfg):
+    gp, gs = syn.init_generator(cfg, seed=42, bias_scale=0.05)
+    dp, ds = syn.init_discriminator(cfg, seed=43, bias_scale=0.05)
+    gen, disc, state = train_utils.create_train_state(cfg, 0)
+    return gen, disc, train_utils.load_flax_params(state, gp, gs, dp, ds)
+
+
+def _batch(cfg, seed=0, d_aug=None, u=None):
+    batch = {k: torch.as_tensor(v) for k, v in syn.make_batch(cfg, per_device_batch=B, seed=seed).items()}
+    if d_aug is not None:
+        batch["d_aug"] = torch.as_tensor(d_aug)
+    if u is not None:
+        batch["d_aug_u"] = torch.as_tensor(u)
+    return batch
+
+
+def _rows(cfg):
+    return B * cfg.d_step_per_g_step
+
+
+def test_replicas_and_bad_gate_tensors_raise(cpu_table):
+    cfg = _cfg(FULL, ada_target=0.6)
+    gen, disc, state = _fresh(cfg)
+    assert state.ada is not None and state.ada.state.dtype == torch.float64 and not state.ada.state.any()
+    plan, u = DA.identity_plan(_rows(cfg)), ADA.draw_gates(1, 1, 0, _rows(cfg))
+    with pytest.raises(ValueError, match="replicas"):
+        train_utils.train_step(1, state, _batch(cfg, d_aug=plan, u=u), xmc_gan, gen, disc, cfg, {}, grad_sync=object())
+    with pytest.raises(ValueError, match="replicas"):
+        xmc_gan.train_d(1, state, train_utils.split_input_dict(_batch(cfg, d_aug=plan, u=u), 2)[0], gen, disc, cfg, grad_sync=object())
+    with pytest.raises(ValueError, match="d_aug_u"):
+        train_utils.train_step(1, state, _batch(cfg, d_aug=plan), xmc_gan, gen, disc, cfg, {})
+    with pytest.raises(ValueError, match="d_aug_u"):
+        train_utils.train_step(1, state, _batch(cfg, d_aug=plan, u=u[:, :, :4]), xmc_gan, gen, disc, cfg, {})
+    assert not state.ada.state.any()                  # nothing reached the controller
+    # a state built without the switch cannot run a step with it
+    gen0, disc0, state0 = _fresh(_cfg(FULL))
+    assert state0.ada is None
+    with pytest.raises(ValueError, match="AdaController"):
+        train_utils.train_step(1, state0, _batch(cfg, d_aug=plan, u=u), xmc_gan, gen0, disc0, cfg, {})
+
+
+# --------------------------------------------------------------------------------------------------------- through the step
+def _step(policy, d_aug=None, ada_p=None, u=None):
+    """one train_step from the same state and batch; ``ada_p``: the switch on, with the controller's p forced to that value"""
+    cfg = _cfg(policy, **({"ada_target": 0.6} if ada_p is not None else {}))
+    gen, disc, state = _fresh(cfg)
+    if ada_p is not None:
+        state.ada.state[0] = ada_p
+    state, metrics = train_utils.train_step(0, state, _batch(cfg, d_aug=d_aug, u=u), xmc_gan, gen, disc, cfg, {})
+    return (state.g_optimizer.arena.params.clone(), state.d_optimizer.arena.params.clone(),
+            {k: float(v) for k, v in metrics.items()}, state)
+
+
+def _same(a, b):
+    return torch.equal(a[0], b[0]) and torch.equal(a[1], b[1]) and a[2] == b[2]
+
+
+def test_p_zero_is_the_switch_off_step_and_the_identity_plan_step(cpu_table):
+    cfg = _cfg(FULL)
+    rows = _rows(cfg)
+    plan = DA.draw_plan(5, 1, 0, rows, cfg.image_size, cfg.image_size, FULL)
+    u = ADA.draw_gates(5, 1, 0, rows)
+    geo = plan.copy()
+    geo[..., :3] = IDENT[:3]
+    assert _same(_step("translation,cutout", geo, ada_p=0.0, u=u), _step(""))
+    got = _step(FULL, plan, ada_p=0.0, u=u)
+    assert _same(got, _step(FULL, DA.identity_plan(rows)))
+    # the controller ran: two half steps of B real logits each, no adjustment yet (ada_interval = 4)
+    s = got[3].ada.state.numpy()
+    assert s[ADA.TICKS] == 2 and s[ADA.COUNT] == 2 * B and s[ADA.P] == 0 and s[ADA.ADJUSTMENTS] == 0
+
+
+def test_p_one_is_the_parents_step_with_the_drawn_plan(cpu_table):
+    cfg = _cfg(FULL)
+    rows = _rows(cfg)
+    plan = DA.draw_plan(5, 1, 0, rows, cfg.image_size, cfg.image_size, FULL)
+    got, want = _step(FULL, plan, ada_p=1.0, u=ADA.draw_gates(5, 1, 0, rows)), _step(FULL, plan)
+    assert _same(got, want)
+    assert got[3].ada.state[0] == 1.0 and want[3].ada is None
+
+
+def test_controller_state_is_the_replay_of_the_logits_it_was_handed(cpu_table, monkeypatch):
+    cfg = _cfg(FULL, ada_target=0.6, ada_kimg=0.016, ada_interval=2)
+    gen, disc, state = _fresh(cfg)
+    seen = []
+    real_update = ADA.AdaController.update
+
+    def recording(self, ops, logit, b):
+        seen.append(logit.detach()[:b].float().cpu().numpy().copy())
+        return real_update(self, ops, logit, b)
+    monkeypatch.setattr(ADA.AdaController, "update", recording)
+    for step in range(1, 4):
+        rows = _rows(cfg)
+        plan = DA.draw_plan(9, step, 0, rows, cfg.image_size, cfg.image_size, FULL)
+        batch = _batch(cfg, seed=step, d_aug=plan, u=ADA.draw_gates(9, step, 0, rows))
+        state, _ = train_utils.train_step(step, state, batch, xmc_gan, gen, disc, cfg, {})
+    assert len(seen) == 3 * cfg.d_step_per_g_step and all(x.shape == (B,) for x in seen)
+    s = ADA.initial_state()
+    for x in seen:
+        s = ADA.update(s, x, 0.6, 16.0, 2, ADA.P_MAX)
+    assert state.ada.state.numpy().tobytes() == s.tobytes()
+    assert s[ADA.ADJUSTMENTS] == 3 and s[ADA.TICKS] == 0
+
+
+# ------------------------------------------------------------------------------------------------------------------- state
+def test_controller_state_travels_in_the_checkpoint(cpu_table):
+    cfg = _cfg(FULL, ada_target=0.6)
+    _, _, state = _fresh(cfg)
+    values = np.array([0.3, -5.0, 14.0, 3.0, 1.0 / 3.0, 17.0, 0.0, 0.0])
+    state.ada.load_state_dict({"state": values})
+    assert state.ada.read() == dict(p=0.3, r_t=1.0 / 3.0, adjustments=17)
+    data = checkpoint.to_bytes(state)
+    tree = checkpoint.msgpack_restore(data)
+    assert tree["ada"]["state"].dtype == np.float64 and tree["ada"]["state"].tobytes() == values.tobytes()
+    _, _, fresh = _fresh(cfg)
+    assert not fresh.ada.state.any()
+    fresh = checkpoint.from_bytes(fresh, data)
+    assert fresh.ada.state.numpy().tobytes() == values.tobytes()
+    # with the switch off the checkpoint has no such entry, and a state with the switch on loads it (the controller starts at 0)
+    _, _, off = _fresh(_cfg(FULL))
+    plain = checkpoint.to_bytes(off)
+    assert "ada" not in checkpoint.msgpack_restore(plain)
+    _, _, fresh = _fresh(cfg)
+    assert not checkpoint.from_bytes(fresh, plain).ada.state.any()

@@ -234,6 +234,8 @@ SIGNATURES = {
     "xmc_adam_wprep_tiles_guarded": [_P, _I, _I, _P, _P, _P, _P, _P, _F, C.c_double, C.c_double, _F, _P, _F, _F, _I, _P, _P, _P, _P, _P, _P,
                                      _P, _P, _P, _P, _P],
     "xmc_metrics_accum_if": [_P, _I, _P, _P, _P, _P],
+    "xmc_ada_gate": [_P, _P, _P, _P, _I, _P],
+    "xmc_ada_update": [_P, _I, _P, C.c_double, C.c_double, _I, C.c_double, _P],
 }
 
 # diagnostic probes: include/xmc_probe.h, libxmc_probe.so (csrc_probe/) -- outside the product ABI

@@ -1059,6 +1059,28 @@ class HipOps:
                                        _code(g.dtype), _p(ws), self._stream()), "xmc_diffaug_bwd")
         return dimg
 
+    # ------------------------------------------------------------------ adaptive discriminator augmentation (libml/ada.py)
+    def ada_gate(self, plan, u, state):
+        """The plan rows of this half step (2B, 8), real half first, from the drawn plan (B, 2, 8) and the uniforms ``u`` (B, 2, 5):
+        part g of a row keeps its drawn values iff float64(u) < state[0], read on the device (``xmc_ada_gate``; specification:
+        ``ada.gate``).  ``state``: the controller's float64[8].  One launch on the current stream (capturable)."""
+        b = plan.shape[0]
+        assert plan.dtype == torch.float32 and tuple(plan.shape) == (b, 2, 8) and plan.is_cuda
+        assert u.dtype == torch.float32 and tuple(u.shape) == (b, 2, 5) and u.device == plan.device
+        assert state.dtype == torch.float64 and state.numel() >= 8 and state.is_contiguous() and state.device == plan.device
+        rows = self.empty((2 * b, 8), torch.float32)
+        check(self.lib.xmc_ada_gate(_p(plan), _p(u), _p(state), _p(rows), b, self._stream()), "xmc_ada_gate")
+        return rows
+
+    def ada_update(self, logit, b, state, target, images_to_full, interval, p_max):
+        """one half step of the controller over the real half ``logit[:b]`` of D's (2B,) float32 logits (``xmc_ada_update``;
+        specification: ``ada.update``): ``state`` (float64[8], persistent) is updated in place.  One launch of one workgroup on
+        the current stream, no atomics, no host read (capturable)."""
+        assert logit.dtype == torch.float32 and logit.dim() == 1 and logit.numel() >= b and logit.is_cuda
+        assert state.dtype == torch.float64 and state.numel() >= 8 and state.is_contiguous() and state.device == logit.device
+        check(self.lib.xmc_ada_update(_p(logit), int(b), _p(state), float(target), float(images_to_full), int(interval), float(p_max),
+                                      self._stream()), "xmc_ada_update")
+
     # ------------------------------------------------------------------ pairwise sample metrics (utils/sample_metrics.py)
     def sample_pool(self, x):
         """an (n, d) float32 pool on this table's device (a NumPy array is uploaded; a device tensor is taken as it is), so that a

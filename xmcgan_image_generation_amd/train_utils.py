@@ -48,6 +48,7 @@ class TrainState:
     pending: Any = None             # deferred "wait for the D gradient exchange + Adam" of a train_d (multi-GPU only)
     prefetched_g: Any = None        # (batch identity, (image, new batch_stats, tape)) of the next train_g_d's generator forward (train_d)
     guard: Any = None               # config.skip_nonfinite_updates: the NonfiniteGuard (verdict + skip counters in device memory)
+    ada: Any = None                 # config.ada_target: the AdaController (p and the controller's counts in device memory)
 
     def replace(self, **kw):
         return dataclasses.replace(self, **kw)
@@ -86,6 +87,8 @@ def create_train_state(config, rng, init_batch=None, ops=None):
     xmc_net.check_config(config)
     from .libml import diff_augment
     diff_augment.parse_policy(config.get("diff_augment", ""))     # ValueError on an unknown part, before anything is allocated
+    from .libml import ada as ada_lib
+    ada_lib.check_config(config)                     # config.ada_target: a policy to gate, settings inside their domains
     ops = ops if ops is not None else xmc_net.make_ops(dtype)
     if config.get("conv_fp8", False):                # BASELINE config #5: MX-fp8 3x3 convolutions (ops.py::_conv_mx8)
         if dtype != torch.bfloat16:
@@ -110,13 +113,14 @@ def create_train_state(config, rng, init_batch=None, ops=None):
     ema_buffer = g_arena.params.clone()                                   # ema_params = generator_params (:170)
     from .libml import nonfinite_guard
     guard = nonfinite_guard.NonfiniteGuard(ops.device) if nonfinite_guard.enabled(config) else None
+    ada = ada_lib.AdaController(ops.device, config) if ada_lib.enabled(config) else None
     state = TrainState(
         step=0,
         g_optimizer=Optimizer(g_arena, config.g_lr, config.beta1, config.beta2),
         d_optimizer=Optimizer(d_arena, config.d_lr, config.beta1, config.beta2),
         generator_state={"batch_stats": g_vars["batch_stats"]},
         discriminator_state={"spectral_norm_stats": d_vars["spectral_norm_stats"]},
-        ema_params=g_arena.tree(ema_buffer), ema_buffer=ema_buffer, guard=guard)
+        ema_params=g_arena.tree(ema_buffer), ema_buffer=ema_buffer, guard=guard, ada=ada)
     return generator, discriminator, state
 
 
@@ -147,6 +151,8 @@ def train_step(rng, state, batch, gan_model=xmc_gan, generator=None, discriminat
         raise ValueError("config.skip_nonfinite_updates is not supported with replicas (grad_sync): the verdict of a half step must "
                          "exist before any of its updates is applied, which the deferred and bucketed discriminator update of the "
                          "data-parallel schedule does not allow")
+    if gan_model is xmc_gan:
+        xmc_gan.check_ada_replicas(config, grad_sync)
     if grad_sync is not None and config.get("batch_norm_group_size", -1) > 0:
         grad_sync.require_groups(generator(train=True).bn_groups)
     parts = split_input_dict(batch, n)
@@ -609,8 +615,10 @@ def train(config, workdir, test_mode=False, *, datasets=None):
     statistics = additional_data.get("statistics")   # config.train_statistics: filled by train_g_d, read at the boundaries below
     graphed, window_start = None, initial_step
     n_split = config.d_step_per_g_step
+    from .libml import ada as ada_lib
     from .libml import diff_augment
     aug_policy = config.get("diff_augment", "")      # differentiable augmentation of D's inputs: a plan per step, like z
+    ada = state.ada if ada_lib.enabled(config) else None       # config.ada_target: p is decided on the device
     clip_guidance = additional_data.get("clip_guidance") if gan_model is xmc_gan else None      # config.clip_guidance_weight > 0
     from .libml import nonfinite_guard
     guard = state.guard if nonfinite_guard.enabled(config) else None      # config.skip_nonfinite_updates: the skip counters
@@ -633,6 +641,8 @@ def train(config, workdir, test_mode=False, *, datasets=None):
             rows, h, w = batch["image"].shape[:3]
             batch["d_aug"] = torch.from_numpy(diff_augment.draw_plan(fold_in(streams["train"], step), step, rank, rows, h, w,
                                                                      aug_policy))
+            if ada is not None:                      # ... and the uniforms its parts are gated with, a stream of their own
+                batch["d_aug_u"] = torch.from_numpy(ada_lib.draw_gates(fold_in(streams["train"], step), step, rank, rows))
         if graphed is None:
             state, metrics = train_step(fold_in(streams["train"], step), state, batch, gan_model, generator, discriminator, config,
                                         additional_data, grad_sync=grad_sync)
@@ -667,6 +677,7 @@ def train(config, workdir, test_mode=False, *, datasets=None):
                                      f"(config.nonfinite_max_consecutive = {nonfinite_guard.max_consecutive(config)}) by step {step}: "
                                      f"the parameters or the data are bad and skipping cannot help; no checkpoint of that state is "
                                      f"written (the newest one is {rotation.latest()}){where}")
+        ada_now = ada.read() if ada is not None else None         # (with the accumulator too: the stream is already drained)
         state = xmc_gan._flush(state)
         if write_scalars:
             # (a window whose every step was skipped has no metric to average: NaN, as 0 / 0 says)
@@ -676,6 +687,8 @@ def train(config, workdir, test_mode=False, *, datasets=None):
                 scalars["guard/longest_run"] = skips["longest"]
                 skipped_before = skips["skipped"]
                 guard.reset_longest()
+            if ada_now is not None:
+                scalars.update({"ada/p": ada_now["p"], "ada/r_t": ada_now["r_t"], "ada/adjustments": ada_now["adjustments"]})
             if statistics is not None:               # this replica's statistics (not averaged over replicas): window means
                 window = statistics.read()
                 if writes:

@@ -111,6 +111,8 @@ def to_state_dict(state) -> Dict[str, Any]:
            "ema_params": _np_tree(state.g_optimizer.arena.tree(state.ema_buffer))}
     if getattr(state, "guard", None) is not None:    # config.skip_nonfinite_updates (not in the reference): the skip counters
         out["nonfinite_guard"] = state.guard.state_dict()
+    if getattr(state, "ada", None) is not None:      # config.ada_target (not in the reference): p and the controller's counts
+        out["ada"] = state.ada.state_dict()
     return out
 
 
@@ -139,6 +141,8 @@ def from_state_dict(state, d: Dict[str, Any]):
     ops = state.g_optimizer.arena.ops
     if getattr(state, "guard", None) is not None and "nonfinite_guard" in d:
         state.guard.load_state_dict(d["nonfinite_guard"])
+    if getattr(state, "ada", None) is not None and "ada" in d:
+        state.ada.load_state_dict(d["ada"])
     return state.replace(step=int(np.asarray(d["step"])),
                          generator_state={k: xmc_net._tree_to_dev(ops, v) for k, v in d["generator_state"].items()},
                          discriminator_state={k: xmc_net._tree_to_dev(ops, v) for k, v in d["discriminator_state"].items()},

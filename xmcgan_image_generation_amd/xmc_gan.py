@@ -22,6 +22,7 @@ import os
 
 import torch
 
+from .libml import ada as ada_lib
 from .libml import attention_lib as attn_lib
 from .libml import diff_augment
 from .libml import losses
@@ -251,10 +252,14 @@ def plan_host_of(aug):
     return aug.detach().to("cpu", torch.float32).numpy()
 
 
-def _augment_d_input(ops, config, batch, real, img):
+def _augment_d_input(ops, config, batch, real, img, ada=None):
     """D's input under config.diff_augment: ``diff_augment(real, img, batch["d_aug"])`` instead of the concatenation -- on HipOps one
     kernel that writes the (2B, H, W, 3) buffer from the two halves.  -> (all_images, (plan rows of the generated half on the
     device, their host copy, flags)) -- all the pullback needs.
+    ``ada`` (config.ada_target: the state's ``AdaController``): the rows are the plan GATED by ``batch["d_aug_u"]`` against the
+    controller's p, on the device (one launch in place of the transpose); the generated half's gated rows go into the tape, so the
+    pullback transposes exactly what the forward applied.  The host copy stays the UNGATED plan: a gated row passes the
+    library's checks whenever the drawn one does (a gated part holds its identity value).
     The host copy is what the library validates before it launches.  Under graph replay only the capture-time plan has been
     validated that way: the replayed plans arrive in the static device tensor, and the kernels' own clamps and bounds checks are
     what keeps such a plan from indexing outside a buffer."""
@@ -269,13 +274,39 @@ def _augment_d_input(ops, config, batch, real, img):
     host = batch["d_aug_host"] if "d_aug_host" in batch else plan_host_of(aug)
     host = torch.as_tensor(host).to(torch.float32).numpy()
     host = host.transpose(1, 0, 2).reshape(2 * b, diff_augment.PLAN_WIDTH).copy()      # rows 0..B-1 real, B..2B-1 generated
-    rows = xmc_net._to_dev(ops, aug).transpose(0, 1).reshape(2 * b, diff_augment.PLAN_WIDTH)
+    if ada is not None:
+        if "d_aug_u" not in batch:
+            raise ValueError("config.ada_target is set but the batch has no 'd_aug_u' (libml/ada.draw_gates: float32 "
+                             "[rows, 2, 5], drawn per step next to 'd_aug')")
+        u = torch.as_tensor(batch["d_aug_u"])
+        if tuple(u.shape) != (b, 2, ada_lib.N_PARTS):
+            raise ValueError(f"batch['d_aug_u'] must be ({b}, 2, {ada_lib.N_PARTS}), got {tuple(u.shape)}")
+        rows = ada.gate(ops, xmc_net._to_dev(ops, aug), xmc_net._to_dev(ops, u))
+    else:
+        rows = xmc_net._to_dev(ops, aug).transpose(0, 1).reshape(2 * b, diff_augment.PLAN_WIDTH)
     if hasattr(ops, "diff_augment"):
         all_images = ops.diff_augment(real.contiguous(), img.contiguous(), rows, host, flags)
     else:
         diff_augment.check_plan(host, *img.shape[1:3])                       # (the library's checks, for the torch executors)
         all_images = diff_augment.apply_torch(torch.cat([real, img], dim=0), rows, flags)
     return all_images, (rows[b:], host[b:], flags)
+
+
+def _ada_of(state, config):
+    """config.ada_target -> the state's ``AdaController`` (ValueError when the state was built without one), else None"""
+    if not ada_lib.enabled(config):
+        return None
+    if getattr(state, "ada", None) is None:
+        raise ValueError("config.ada_target is set but the TrainState has no AdaController (state.ada): build the state with "
+                         "create_train_state under the same config")
+    return state.ada
+
+
+def check_ada_replicas(config, grad_sync):
+    """config.ada_target with replicas is an error, the same decision as for config.skip_nonfinite_updates"""
+    if grad_sync is not None and ada_lib.enabled(config):
+        raise ValueError("config.ada_target is not supported with replicas (grad_sync): every replica would run a controller of "
+                         "its own on its own logits, their p would drift apart, and only rank 0's would be checkpointed")
 
 
 def _augment_pullback(ops, d_tape, dimg):
@@ -345,7 +376,7 @@ def _forward(rng, config, state, batch, g, d, need_g_tape, image_model=None, aft
     real = ops.cast(xmc_net._to_dev(ops, batch["image"]), ops.dtype)
     aug_ctx = None
     if config.get("diff_augment", ""):       # (not in the reference) the frozen ResNet-50 term below keeps the plain real / img
-        all_images, aug_ctx = _augment_d_input(ops, config, batch, real, img)
+        all_images, aug_ctx = _augment_d_input(ops, config, batch, real, img, ada=_ada_of(state, config))
     else:
         all_images = torch.cat([real, img], dim=0)                           # xmc_gan.py:140,233
     if _ovl(ops, _OVERLAP_PREP) and not deferred and not prep_on_main:
@@ -377,6 +408,11 @@ def _forward(rng, config, state, batch, g, d, need_g_tape, image_model=None, aft
                                                 **({"want_stats": True} if stats is not None else {}))
     if stats is not None:
         stats.note_forward(logit, loss_vec, d.last_stats, d._sn_ctx[3])
+    if aug_ctx is not None and _ada_of(state, config) is not None:
+        # config.ada_target: the controller reads the real half of the logits on the stream the discriminator's forward ran on
+        # -- the next half step's gate reads the new p in stream order.  Forward values only: not under the non-finite guard's
+        # verdict (non-finite logits are not counted)
+        state.ada.update(ops, logit, img.shape[0])
     if aug_ctx is not None:
         d_tape["d_aug"] = aug_ctx            # train_g_d pulls the generated half's gradient back through it
     b = img.shape[0]
@@ -539,6 +575,7 @@ def train_d(rng, state, batch, generator, discriminator, config, grad_sync=None,
     ops = g.ops
     if hasattr(ops, "begin_pool"):
         ops.begin_pool()
+    check_ada_replicas(config, grad_sync)
     state, guard = _guarded(state, config, ops, g, d, grad_sync)
     d_arena = state.d_optimizer.arena
     deferred_in = getattr(state, "pending", None) is not None
@@ -612,6 +649,7 @@ def train_g_d(rng, state, batch, generator, discriminator, config, additional_da
     ops = g.ops
     if hasattr(ops, "begin_pool"):
         ops.begin_pool()
+    check_ada_replicas(config, grad_sync)
     state, guard = _guarded(state, config, ops, g, d, grad_sync)
     d_arena, g_arena = state.d_optimizer.arena, state.g_optimizer.arena
     if getattr(state, "pending", None) is None:
