@@ -1083,6 +1083,28 @@ int xmc_ada_gate(const float* plan, const float* u, const double* state, float* 
 int xmc_ada_update(const float* logit, int32_t b, double* state, double target, double images_to_full, int32_t interval,
                    double p_max, void* stream);
 
+/* ---- LeCam discriminator regulariser (config.lecam_weight; libml/lecam.py is the specification; csrc/lecam.hip) ----
+ * XMC_ABI_VERSION stays 36: this section only ADDS an entry point, as the section above did.
+ * `state` is the regulariser's persistent float64[8] in device memory, 8-byte aligned (the caller zeroes it once):
+ *     [0] anchor_real   [1] anchor_fake   [2] ticks (half steps seen)   [3] last R   [4] updates (anchor updates applied)
+ *     [5] .. [7] not touched
+ *  - xmc_lecam: one half step over logit[0 .. 2b) = D's float32 logits [real; fake] and dld[0 .. 2b), the gradient xmc_hinge has
+ *    just written.  In IEEE double, in this order, no multiply fused with an add; S is the fixed-order sum "lane j of 256 adds
+ *    elements j, j + 256, ... in rising order onto +0, then the tree v[j] += v[j + s] for s = 128 ... 1":
+ *      1. active = ticks >= start and updates > 0.
+ *      2. if active: dr_i = real_i - anchor_fake, df_i = fake_i - anchor_real (one_sided: dr_i = dr_i > 0 ? dr_i : 0 and
+ *         df_i = df_i < 0 ? df_i : 0);  R = (S(dr^2) + S(df^2)) / b;  c = (2 lam) / b;  dld_i = float32(double(dld_i) + c d_i), one
+ *         rounding per element.  Otherwise R = 0 and dld is not written.  last R = R, loss[0] = float32(R): the UNWEIGHTED value,
+ *         written, not added.  A NaN that is written (an element of dld, R) is the canonical quiet NaN (sign 0, payload 0).
+ *      3. if all 2b logits are finite: m_R = S(real) / b, m_F = S(fake) / b;  g = active ? decay : 0;  anchor = g * anchor +
+ *         (1 - g) * m for both anchors, from the values read in 1 (two multiplies and an add, each rounded);  updates += 1.
+ *      4. ticks += 1.
+ *    One workgroup of 256, no atomics: bit-equal to the specification.  Writes dld[0 .. 2b), loss[0], state[0 .. 5), nothing else.
+ *    Domain: 1 <= b, 2 b <= 2147483647; lam finite and >= 0; 0 <= decay < 1; start >= 0; one_sided 0 or 1; logit, dld and loss
+ *    4-byte aligned.  Anything else returns XMC_EINVAL and launches nothing. */
+int xmc_lecam(const float* logit, float* dld, int32_t b, double* state, float* loss, double lam, double decay, int32_t start,
+              int32_t one_sided, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

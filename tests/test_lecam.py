@@ -1,0 +1,352 @@
+"""config.lecam_weight without a GPU: the NumPy specification of the regulariser (libml/lecam.py) against float64 autograd, its state
+machine, the configuration errors, the switch through ``train_step`` on the CPU operator table (tests/cpu_ops.py has no ``lecam``:
+the controller takes the specification), and the controller's state through a checkpoint."""
+import numpy as np
+import pytest
+import torch
+
+from tests.cpu_ops import CpuOps
+from xmcgan_image_generation_amd import synthetic as syn
+from xmcgan_image_generation_amd import train_utils, xmc_gan
+from xmcgan_image_generation_amd.configs import coco_xmc
+from xmcgan_image_generation_amd.libml import lecam as LC
+from xmcgan_image_generation_amd.nets import xmc_net
+from xmcgan_image_generation_amd.utils import checkpoint
+
+KEYS = ("lecam_weight", "lecam_decay", "lecam_start", "lecam_one_sided")
+
+
+@pytest.fixture(scope="module")
+def cpu_table():
+    xmc_net.set_ops_factory(lambda dtype: CpuOps(dtype))
+    yield
+    xmc_net.set_ops_factory(None)
+
+
+def _bits(x):
+    x = np.atleast_1d(np.asarray(x))
+    return x.view(np.uint64 if x.dtype == np.float64 else np.uint32).tolist()
+
+
+def _logits(b, seed):
+    """(2b,) float32 with magnitudes from 1e-3 to 1e3 and both signs"""
+    rng = np.random.default_rng(seed)
+    return (rng.standard_normal(2 * b) * 10.0 ** rng.uniform(-3, 3, 2 * b)).astype(np.float32)
+
+
+def _hinge_dld(x, b):
+    """what the hinge launch writes: -[1 - real > 0] / b and [1 + fake > 0] / b, in float32"""
+    r, f = x[:b], x[b:]
+    return np.concatenate([-(1 - r > 0).astype(np.float32) / np.float32(b), (1 + f > 0).astype(np.float32) / np.float32(b)])
+
+
+def _active_state(a_r=0.75, a_f=-0.4):
+    s = LC.initial_state()
+    s[LC.ANCHOR_REAL], s[LC.ANCHOR_FAKE], s[LC.TICKS], s[LC.UPDATES] = a_r, a_f, 6.0, 6.0
+    return s
+
+
+# ------------------------------------------------------------------------------------------------------------- fixed_sum
+def test_fixed_sum_is_the_lane_and_tree_order_written_out():
+    rng = np.random.default_rng(3)
+    for n in (1, 5, 255, 256, 257, 600, 1300):
+        x = rng.standard_normal(n) * 10.0 ** rng.uniform(-6, 6, n)
+        v = [0.0] * 256
+        for i in range(n):                                                # lane j adds j, j + 256, ... in rising order
+            v[i % 256] = v[i % 256] + float(x[i])
+        s = 128
+        while s >= 1:
+            for j in range(s):
+                v[j] = v[j] + v[j + s]
+            s //= 2
+        assert _bits(np.float64(LC.fixed_sum(x))) == _bits(np.float64(v[0])), n
+    assert LC.fixed_sum(np.array([-0.0])) == 0.0 and not np.signbit(LC.fixed_sum(np.array([-0.0])))
+
+
+# ---------------------------------------------------------------------------------------- specification against autograd
+@pytest.mark.parametrize("start_from", ["zeros", "hinge"])
+@pytest.mark.parametrize("one_sided", [False, True])
+@pytest.mark.parametrize("b", [1, 5, 300])
+def test_specification_against_float64_autograd(b, one_sided, start_from):
+    lam, state = 0.3, _active_state()
+    x = _logits(b, 100 + b)
+    x[0] = np.float32(state[LC.ANCHOR_FAKE])                              # a tie: real_0 == a_F (float32-representable: -0.4 is not)
+    state[LC.ANCHOR_FAKE] = np.float64(x[0])
+    dld = np.zeros(2 * b, np.float32) if start_from == "zeros" else _hinge_dld(x, b)
+    new, got, r = LC.step(state, x, b, dld, lam, 0.99, 0, one_sided)
+    t = torch.tensor(x.astype(np.float64), requires_grad=True)
+    a_r, a_f = float(state[LC.ANCHOR_REAL]), float(state[LC.ANCHOR_FAKE])
+    if one_sided:
+        dr, df = torch.relu(t[:b] - a_f), torch.relu(a_r - t[b:])
+    else:
+        dr, df = t[:b] - a_f, t[b:] - a_r
+    big_r = (dr * dr).sum() / b + (df * df).sum() / b
+    (lam * big_r).backward()
+    v_auto = dld.astype(np.float64) + t.grad.numpy()
+    want = v_auto.astype(np.float32)
+    # the specification's own float64 value, written out: one rounding of it is what must have been stored
+    d = np.concatenate([x[:b].astype(np.float64) - a_f, x[b:].astype(np.float64) - a_r])
+    if one_sided:
+        d = np.concatenate([np.where(d[:b] > 0, d[:b], 0.0), np.where(d[b:] < 0, d[b:], 0.0)])
+    v_spec = dld.astype(np.float64) + ((2.0 * lam) / b) * d
+    assert got.dtype == np.float32 and _bits(got) == _bits(v_spec.astype(np.float32))
+    differ = np.flatnonzero(got.view(np.uint32) != want.view(np.uint32))
+    print(f"b={b} one_sided={one_sided} {start_from}: {len(differ)} of {2 * b} elements differ from float32(dld + g_autograd); "
+          f"R spec {float(new[LC.LAST_R])!r} autograd {big_r.item()!r}")
+    for i in differ:                                                      # within 1 ulp, and only across a rounding boundary
+        lo, hi = sorted((float(got[i]), float(want[i])))
+        assert np.nextafter(np.float32(lo), np.float32(np.inf)) == np.float32(hi), (i, got[i], want[i])
+        boundary = (lo + hi) / 2.0
+        assert min(v_spec[i], v_auto[i]) <= boundary <= max(v_spec[i], v_auto[i]), (i, v_spec[i], v_auto[i])
+    assert abs(float(new[LC.LAST_R]) - big_r.item()) <= b * 2.0 ** -52 * float(np.max(d * d))
+    assert r.dtype == np.float32 and r == np.float32(new[LC.LAST_R]) and new[LC.LAST_R] > 0
+    if one_sided:                                                         # zero gradient exactly where the sign is excluded
+        raw = np.concatenate([x[:b].astype(np.float64) - a_f, x[b:].astype(np.float64) - a_r])
+        off = np.concatenate([raw[:b] <= 0, raw[b:] >= 0])
+        assert off.any() and (~off).any()
+        assert _bits(got[off]) == _bits((dld[off].astype(np.float64) + 0.0).astype(np.float32))
+        assert (got[~off] != dld[~off]).mean() > 0.5
+    assert _bits(got[:1]) == _bits((dld[:1].astype(np.float64) + 0.0).astype(np.float32))       # the tie: no gradient in either form
+
+
+# --------------------------------------------------------------------------------------------------------- state machine
+def _run(sets, b, lam=0.3, decay=0.9, start=0, one_sided=False, state=None):
+    s = LC.initial_state() if state is None else np.asarray(state, np.float64)
+    out = []
+    for x in sets:
+        dld = _hinge_dld(np.asarray(x, np.float32), b)
+        s, g, r = LC.step(s, x, b, dld, lam, decay, start, one_sided)
+        out.append((s.copy(), g, r, dld))
+    return out
+
+
+def test_warm_up_copies_the_means_and_leaves_dld():
+    b = 5
+    xs = [_logits(b, 10 + i) for i in range(3)]
+    hist = _run(xs, b, start=3)
+    for i, (s, g, r, dld) in enumerate(hist):
+        x = xs[i].astype(np.float64)
+        assert s[LC.ANCHOR_REAL] == LC.fixed_sum(x[:b]) / b and s[LC.ANCHOR_FAKE] == LC.fixed_sum(x[b:]) / b
+        assert s[LC.TICKS] == i + 1 and s[LC.UPDATES] == i + 1 and s[LC.LAST_R] == 0 and r == 0
+        assert _bits(g) == _bits(dld)
+        assert not s[5:].any()
+
+
+def test_first_update_ignores_the_decay_and_the_second_uses_it():
+    b = 4
+    x0, x1 = _logits(b, 1), _logits(b, 2)
+    (s0, g0, r0, dld0), (s1, g1, r1, dld1) = _run([x0, x1], b, decay=0.9)
+    m0 = (LC.fixed_sum(x0[:b].astype(np.float64)) / b, LC.fixed_sum(x0[b:].astype(np.float64)) / b)
+    assert (s0[LC.ANCHOR_REAL], s0[LC.ANCHOR_FAKE]) == m0 and _bits(g0) == _bits(dld0) and r0 == 0     # never biased towards 0
+    m1 = (LC.fixed_sum(x1[:b].astype(np.float64)) / b, LC.fixed_sum(x1[b:].astype(np.float64)) / b)
+    k = np.float64(1.0) - np.float64(0.9)
+    assert s1[LC.ANCHOR_REAL] == np.float64(0.9) * m0[0] + k * m1[0]
+    assert s1[LC.ANCHOR_FAKE] == np.float64(0.9) * m0[1] + k * m1[1]
+    assert s1[LC.UPDATES] == 2 and r1 > 0 and _bits(g1) != _bits(dld1)    # the term is on from the second half step (start = 0)
+    # the penalty of the second call used the anchors of the FIRST, not the ones it was about to write
+    d = np.concatenate([x1[:b].astype(np.float64) - m0[1], x1[b:].astype(np.float64) - m0[0]])
+    assert _bits(g1) == _bits((dld1.astype(np.float64) + ((2.0 * 0.3) / b) * d).astype(np.float32))
+
+
+def test_the_term_switches_on_at_start():
+    b = 3
+    xs = [_logits(b, 20 + i) for i in range(6)]
+    hist = _run(xs, b, start=4)
+    for i, (s, g, r, dld) in enumerate(hist):
+        assert (r > 0) == (i >= 4) and (_bits(g) != _bits(dld)) == (i >= 4), i
+        assert s[LC.TICKS] == i + 1
+    # the decay starts with the term: call 4 (ticks = 4 >= start) is the first that averages
+    s3, s4, x4 = hist[3][0], hist[4][0], xs[4].astype(np.float64)
+    k = np.float64(1.0) - np.float64(0.9)
+    assert s4[LC.ANCHOR_REAL] == np.float64(0.9) * s3[LC.ANCHOR_REAL] + k * (LC.fixed_sum(x4[:b]) / b)
+
+
+@pytest.mark.parametrize("bad", [np.nan, np.inf, -np.inf])
+@pytest.mark.parametrize("half", [0, 1])
+@pytest.mark.parametrize("active", [False, True])
+def test_a_non_finite_logit_moves_no_anchor_and_still_ticks(bad, half, active):
+    b = 5
+    x = _logits(b, 7)
+    x[half * b + 2] = bad
+    state = _active_state() if active else LC.initial_state()
+    ((s, g, r, dld),) = _run([x], b, state=state.copy())
+    assert _bits(s[[LC.ANCHOR_REAL, LC.ANCHOR_FAKE, LC.UPDATES]]) == _bits(state[[LC.ANCHOR_REAL, LC.ANCHOR_FAKE, LC.UPDATES]])
+    assert s[LC.TICKS] == state[LC.TICKS] + 1
+    if not active:
+        assert r == 0 and _bits(g) == _bits(dld)
+    elif np.isnan(bad):
+        assert _bits(np.float64(s[LC.LAST_R])) == [0x7FF8000000000000] and _bits(np.float32(r)) == [0x7FC00000]
+        assert _bits(g[half * b + 2: half * b + 3]) == [0x7FC00000]
+    else:
+        assert s[LC.LAST_R] == np.inf and np.isinf(g[half * b + 2])
+
+
+def test_one_sided_gives_zero_gradient_where_the_difference_has_the_excluded_sign():
+    b = 4
+    state = _active_state(a_r=1.0, a_f=-1.0)
+    x = np.array([-3.0, -1.0, 0.5, 2.0, -2.0, 1.0, 1.5, 0.25], np.float32)        # real - a_F: -2, 0, 1.5, 3; fake - a_R: -3, 0, .5, -.75
+    dld = np.zeros(8, np.float32)
+    _, g, r = LC.step(state, x, b, dld, 0.5, 0.99, 0, True)
+    c = (2.0 * 0.5) / b
+    assert g.tolist() == [0.0, 0.0, np.float32(c * 1.5), np.float32(c * 3.0), np.float32(c * -3.0), 0.0, 0.0, np.float32(c * -0.75)]
+    assert r == np.float32((1.5 ** 2 + 3.0 ** 2 + 3.0 ** 2 + 0.75 ** 2) / b)
+    _, g2, r2 = LC.step(state, x, b, dld, 0.5, 0.99, 0, False)
+    assert (g2 != 0).sum() == 6 and r2 > r
+
+
+def test_step_rejects_shapes_that_are_not_2b():
+    with pytest.raises(ValueError):
+        LC.step(LC.initial_state(), np.zeros(5, np.float32), 2, np.zeros(4, np.float32), 0.3, 0.99, 0)
+    with pytest.raises(ValueError):
+        LC.step(LC.initial_state(), np.zeros(0, np.float32), 0, np.zeros(0, np.float32), 0.3, 0.99, 0)
+
+
+# ----------------------------------------------------------------------------------------------------------- configuration
+B = 4
+
+
+def _cfg(**kw):
+    cfg = coco_xmc.get_test_config()
+    cfg.batch_size = B
+    cfg.update(kw)
+    return cfg
+
+
+def test_the_keys_are_absent_from_every_config():
+    for cfg in (coco_xmc.get_config(), coco_xmc.get_test_config()):
+        assert all(k not in cfg for k in KEYS)
+        assert not LC.enabled(cfg)
+        assert xmc_gan.metric_keys(cfg) == xmc_gan.METRIC_KEYS
+    assert LC.settings(_cfg(lecam_weight=0.3)) == dict(weight=0.3, decay=0.99, start=0, one_sided=False)
+    assert not LC.enabled(_cfg(lecam_weight=0)) and not LC.enabled(_cfg(lecam_weight=0.0))
+    assert xmc_gan.metric_keys(_cfg(lecam_weight=0.3)) == xmc_gan.METRIC_KEYS + ("d_loss_lecam",)
+    assert xmc_gan.metric_keys(_cfg(lecam_weight=0.0)) == xmc_gan.METRIC_KEYS
+
+
+@pytest.mark.parametrize("kw, match", [(dict(lecam_weight=-0.1), "lecam_weight"), (dict(lecam_weight=float("nan")), "lecam_weight"),
+                                       (dict(lecam_weight=float("inf")), "lecam_weight"),
+                                       (dict(lecam_weight=0.3, lecam_decay=1.0), "lecam_decay"),
+                                       (dict(lecam_weight=0.3, lecam_decay=-0.01), "lecam_decay"),
+                                       (dict(lecam_weight=0.3, lecam_decay=float("nan")), "lecam_decay"),
+                                       (dict(lecam_weight=0.3, lecam_start=-1), "lecam_start")])
+def test_create_train_state_rejects_bad_settings_before_it_allocates(kw, match):
+    made = []
+    xmc_net.set_ops_factory(lambda dtype: made.append(dtype) or CpuOps(dtype))
+    try:
+        with pytest.raises(ValueError, match=match):
+            train_utils.create_train_state(_cfg(**kw), 0)
+    finally:
+        xmc_net.set_ops_factory(None)
+    assert not made                                   # not even the operator table was built
+
+
+def _fresh(cfg):
+    gp, gs = syn.init_generator(cfg, seed=42, bias_scale=0.05)
+    dp, ds = syn.init_discriminator(cfg, seed=43, bias_scale=0.05)
+    gen, disc, state = train_utils.create_train_state(cfg, 0)
+    return gen, disc, train_utils.load_flax_params(state, gp, gs, dp, ds)
+
+
+def _batch(cfg, seed=0):
+    return {k: torch.as_tensor(v) for k, v in syn.make_batch(cfg, per_device_batch=B, seed=seed).items()}
+
+
+def test_replicas_raise_and_a_state_without_the_controller_cannot_run_the_switch(cpu_table):
+    cfg = _cfg(lecam_weight=0.3)
+    gen, disc, state = _fresh(cfg)
+    assert state.lecam is not None and state.lecam.state.dtype == torch.float64 and not state.lecam.state.any()
+    with pytest.raises(ValueError, match="replicas"):
+        train_utils.train_step(1, state, _batch(cfg), xmc_gan, gen, disc, cfg, {}, grad_sync=object())
+    with pytest.raises(ValueError, match="replicas"):
+        xmc_gan.train_d(1, state, train_utils.split_input_dict(_batch(cfg), 2)[0], gen, disc, cfg, grad_sync=object())
+    with pytest.raises(ValueError, match="replicas"):
+        xmc_gan.train_g_d(1, state, train_utils.split_input_dict(_batch(cfg), 2)[1], gen, disc, cfg, {}, grad_sync=object())
+    assert not state.lecam.state.any()                # nothing reached the controller
+    gen0, disc0, state0 = _fresh(_cfg())
+    assert state0.lecam is None
+    with pytest.raises(ValueError, match="LecamController"):
+        train_utils.train_step(1, state0, _batch(cfg), xmc_gan, gen0, disc0, cfg, {})
+
+
+# --------------------------------------------------------------------------------------------------------- through the step
+def test_key_absent_is_the_parents_step(cpu_table):
+    cfg = _cfg()
+    gen, disc, state = _fresh(cfg)
+    assert state.lecam is None
+    state, metrics = train_utils.train_step(0, state, _batch(cfg), xmc_gan, gen, disc, cfg, {})
+    assert tuple(metrics) == xmc_gan.METRIC_KEYS and state.lecam is None
+    # ... and lecam_weight = 0 is the key absent, bit for bit
+    cfg0 = _cfg(lecam_weight=0.0)
+    gen0, disc0, state0 = _fresh(cfg0)
+    state0, metrics0 = train_utils.train_step(0, state0, _batch(cfg0), xmc_gan, gen0, disc0, cfg0, {})
+    assert state0.lecam is None and {k: float(v) for k, v in metrics0.items()} == {k: float(v) for k, v in metrics.items()}
+    assert torch.equal(state0.d_optimizer.arena.params, state.d_optimizer.arena.params)
+
+
+@pytest.mark.parametrize("one_sided", [False, True])
+def test_metric_and_state_are_the_replay_of_what_the_controller_was_handed(cpu_table, monkeypatch, one_sided):
+    cfg = _cfg(lecam_weight=0.3, lecam_decay=0.9, lecam_start=1, lecam_one_sided=one_sided)
+    gen, disc, state = _fresh(cfg)
+    seen = []
+    real_apply = LC.LecamController.apply
+
+    def recording(self, ops, logit, dld, b):
+        before = (logit.detach().float().numpy().copy(), dld.detach().numpy().copy(), int(b))
+        r = real_apply(self, ops, logit, dld, b)
+        seen.append(before + (dld.detach().numpy().copy(), float(r[0])))
+        return r
+    monkeypatch.setattr(LC.LecamController, "apply", recording)
+    per_step = []
+    for step in range(1, 4):
+        state, metrics = train_utils.train_step(step, state, _batch(cfg, seed=step), xmc_gan, gen, disc, cfg, {})
+        assert sorted(metrics) == sorted(xmc_gan.METRIC_KEYS + ("d_loss_lecam",)) == sorted(xmc_gan.metric_keys(cfg))
+        per_step.append(float(metrics["d_loss_lecam"]))
+    n = cfg.d_step_per_g_step
+    assert len(seen) == 3 * n and all(x[0].shape == (2 * B,) and x[2] == B for x in seen)
+    s = LC.initial_state()
+    for i, (logit, dld, b, after, r_seen) in enumerate(seen):
+        s, g, r = LC.step(s, logit, b, dld, 0.3, 0.9, 1, one_sided)
+        assert _bits(g) == _bits(after) and float(r) == r_seen
+        assert (r > 0) == (i >= 1) or one_sided
+        if i % n == n - 1:                                                # train_g_d's half step is the one that reports
+            assert per_step[i // n] == float(r)
+    assert state.lecam.state.numpy().tobytes() == s.tobytes()
+    assert s[LC.TICKS] == 3 * n and s[LC.UPDATES] == 3 * n and per_step[-1] > 0
+    assert state.lecam.read() == dict(anchor_real=s[0], anchor_fake=s[1], updates=3 * n, ticks=3 * n, last_r=s[3])
+
+
+def test_the_term_changes_d_and_leaves_g_loss_and_d_loss_definitions(cpu_table):
+    """anchors preloaded so that the term is on from the first half step: D's parameters move away from the parent's, while the
+    metrics of the FIRST step's forward (d_loss = hinge + contrastive, g_loss) differ only through train_d's different update"""
+    cfg, off = _cfg(lecam_weight=0.3), _cfg()
+    gen, disc, state = _fresh(cfg)
+    state.lecam.load_state_dict({"state": _active_state()})
+    gen0, disc0, state0 = _fresh(off)
+    half = train_utils.split_input_dict(_batch(cfg), 2)[0]
+    state = xmc_gan.train_d(0, state, half, gen, disc, cfg)
+    state0 = xmc_gan.train_d(0, state0, half, gen0, disc0, off)
+    assert not torch.equal(state.d_optimizer.arena.params, state0.d_optimizer.arena.params)
+    assert torch.equal(state.g_optimizer.arena.params, state0.g_optimizer.arena.params)
+    assert state.lecam.read()["ticks"] == 7 and state.lecam.read()["last_r"] > 0
+
+
+# ------------------------------------------------------------------------------------------------------------------- state
+def test_controller_state_travels_in_the_checkpoint(cpu_table):
+    cfg = _cfg(lecam_weight=0.3)
+    _, _, state = _fresh(cfg)
+    values = np.array([0.3, -5.0 / 3.0, 14.0, 1.0 / 3.0, 13.0, 0.0, 0.0, 0.0])
+    state.lecam.load_state_dict({"state": values})
+    assert state.lecam.read() == dict(anchor_real=0.3, anchor_fake=-5.0 / 3.0, updates=13, ticks=14, last_r=1.0 / 3.0)
+    data = checkpoint.to_bytes(state)
+    tree = checkpoint.msgpack_restore(data)
+    assert tree["lecam"]["state"].dtype == np.float64 and tree["lecam"]["state"].tobytes() == values.tobytes()
+    _, _, fresh = _fresh(cfg)
+    assert not fresh.lecam.state.any()
+    fresh = checkpoint.from_bytes(fresh, data)
+    assert fresh.lecam.state.numpy().tobytes() == values.tobytes()
+    # with the switch off the checkpoint has no such entry, and a state with the switch on loads it (the anchors start at 0)
+    _, _, off = _fresh(_cfg())
+    plain = checkpoint.to_bytes(off)
+    assert "lecam" not in checkpoint.msgpack_restore(plain)
+    _, _, fresh = _fresh(cfg)
+    assert not checkpoint.from_bytes(fresh, plain).lecam.state.any()

@@ -1081,6 +1081,21 @@ class HipOps:
         check(self.lib.xmc_ada_update(_p(logit), int(b), _p(state), float(target), float(images_to_full), int(interval), float(p_max),
                                       self._stream()), "xmc_ada_update")
 
+    # ------------------------------------------------------------------ LeCam discriminator regulariser (libml/lecam.py)
+    def lecam(self, logit, dld, b, state, lam, decay, start, one_sided):
+        """one half step of the regulariser (``xmc_lecam``; specification: ``lecam.step``): ``dld`` (2B,), the gradient ``hinge``
+        wrote for D's float32 logits ``logit`` = [real; fake], takes 2 lam / b * (logit - anchor) IN PLACE, and ``state``
+        (float64[8], persistent) its anchor update.  -> (1,) float32: the unweighted R.  One launch of one workgroup on the current
+        stream, no atomics, no host read (capturable)."""
+        b = int(b)
+        assert logit.dtype == torch.float32 and logit.dim() == 1 and logit.numel() == 2 * b and logit.is_cuda
+        assert dld.dtype == torch.float32 and dld.dim() == 1 and dld.numel() == 2 * b and dld.device == logit.device
+        assert state.dtype == torch.float64 and state.numel() >= 8 and state.is_contiguous() and state.device == logit.device
+        loss = self.zeros((1,))
+        check(self.lib.xmc_lecam(_p(logit), _p(dld), b, _p(state), _p(loss), float(lam), float(decay), int(start), int(bool(one_sided)),
+                                 self._stream()), "xmc_lecam")
+        return loss
+
     # ------------------------------------------------------------------ pairwise sample metrics (utils/sample_metrics.py)
     def sample_pool(self, x):
         """an (n, d) float32 pool on this table's device (a NumPy array is uploaded; a device tensor is taken as it is), so that a

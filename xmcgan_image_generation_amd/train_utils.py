@@ -49,6 +49,7 @@ class TrainState:
     prefetched_g: Any = None        # (batch identity, (image, new batch_stats, tape)) of the next train_g_d's generator forward (train_d)
     guard: Any = None               # config.skip_nonfinite_updates: the NonfiniteGuard (verdict + skip counters in device memory)
     ada: Any = None                 # config.ada_target: the AdaController (p and the controller's counts in device memory)
+    lecam: Any = None               # config.lecam_weight: the LecamController (the two anchors in device memory)
 
     def replace(self, **kw):
         return dataclasses.replace(self, **kw)
@@ -89,6 +90,8 @@ def create_train_state(config, rng, init_batch=None, ops=None):
     diff_augment.parse_policy(config.get("diff_augment", ""))     # ValueError on an unknown part, before anything is allocated
     from .libml import ada as ada_lib
     ada_lib.check_config(config)                     # config.ada_target: a policy to gate, settings inside their domains
+    from .libml import lecam as lecam_lib
+    lecam_lib.check_config(config)                   # config.lecam_weight / _decay / _start: inside their domains
     ops = ops if ops is not None else xmc_net.make_ops(dtype)
     if config.get("conv_fp8", False):                # BASELINE config #5: MX-fp8 3x3 convolutions (ops.py::_conv_mx8)
         if dtype != torch.bfloat16:
@@ -114,13 +117,14 @@ def create_train_state(config, rng, init_batch=None, ops=None):
     from .libml import nonfinite_guard
     guard = nonfinite_guard.NonfiniteGuard(ops.device) if nonfinite_guard.enabled(config) else None
     ada = ada_lib.AdaController(ops.device, config) if ada_lib.enabled(config) else None
+    lecam = lecam_lib.LecamController(ops.device, config) if lecam_lib.enabled(config) else None
     state = TrainState(
         step=0,
         g_optimizer=Optimizer(g_arena, config.g_lr, config.beta1, config.beta2),
         d_optimizer=Optimizer(d_arena, config.d_lr, config.beta1, config.beta2),
         generator_state={"batch_stats": g_vars["batch_stats"]},
         discriminator_state={"spectral_norm_stats": d_vars["spectral_norm_stats"]},
-        ema_params=g_arena.tree(ema_buffer), ema_buffer=ema_buffer, guard=guard, ada=ada)
+        ema_params=g_arena.tree(ema_buffer), ema_buffer=ema_buffer, guard=guard, ada=ada, lecam=lecam)
     return generator, discriminator, state
 
 
@@ -153,6 +157,7 @@ def train_step(rng, state, batch, gan_model=xmc_gan, generator=None, discriminat
                          "data-parallel schedule does not allow")
     if gan_model is xmc_gan:
         xmc_gan.check_ada_replicas(config, grad_sync)
+        xmc_gan.check_lecam_replicas(config, grad_sync)
     if grad_sync is not None and config.get("batch_norm_group_size", -1) > 0:
         grad_sync.require_groups(generator(train=True).bn_groups)
     parts = split_input_dict(batch, n)
@@ -619,6 +624,8 @@ def train(config, workdir, test_mode=False, *, datasets=None):
     from .libml import diff_augment
     aug_policy = config.get("diff_augment", "")      # differentiable augmentation of D's inputs: a plan per step, like z
     ada = state.ada if ada_lib.enabled(config) else None       # config.ada_target: p is decided on the device
+    from .libml import lecam as lecam_lib
+    lecam = state.lecam if lecam_lib.enabled(config) and gan_model is xmc_gan else None      # config.lecam_weight: the anchors
     clip_guidance = additional_data.get("clip_guidance") if gan_model is xmc_gan else None      # config.clip_guidance_weight > 0
     from .libml import nonfinite_guard
     guard = state.guard if nonfinite_guard.enabled(config) else None      # config.skip_nonfinite_updates: the skip counters
@@ -678,6 +685,7 @@ def train(config, workdir, test_mode=False, *, datasets=None):
                                      f"the parameters or the data are bad and skipping cannot help; no checkpoint of that state is "
                                      f"written (the newest one is {rotation.latest()}){where}")
         ada_now = ada.read() if ada is not None else None         # (with the accumulator too: the stream is already drained)
+        lecam_now = lecam.read() if lecam is not None else None   # (likewise)
         state = xmc_gan._flush(state)
         if write_scalars:
             # (a window whose every step was skipped has no metric to average: NaN, as 0 / 0 says)
@@ -689,6 +697,9 @@ def train(config, workdir, test_mode=False, *, datasets=None):
                 guard.reset_longest()
             if ada_now is not None:
                 scalars.update({"ada/p": ada_now["p"], "ada/r_t": ada_now["r_t"], "ada/adjustments": ada_now["adjustments"]})
+            if lecam_now is not None:
+                scalars.update({"lecam/anchor_real": lecam_now["anchor_real"], "lecam/anchor_fake": lecam_now["anchor_fake"],
+                                "lecam/updates": lecam_now["updates"]})
             if statistics is not None:               # this replica's statistics (not averaged over replicas): window means
                 window = statistics.read()
                 if writes:

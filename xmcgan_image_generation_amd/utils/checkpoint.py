@@ -113,6 +113,8 @@ def to_state_dict(state) -> Dict[str, Any]:
         out["nonfinite_guard"] = state.guard.state_dict()
     if getattr(state, "ada", None) is not None:      # config.ada_target (not in the reference): p and the controller's counts
         out["ada"] = state.ada.state_dict()
+    if getattr(state, "lecam", None) is not None:    # config.lecam_weight (not in the reference): the anchors and their counts
+        out["lecam"] = state.lecam.state_dict()
     return out
 
 
@@ -143,6 +145,8 @@ def from_state_dict(state, d: Dict[str, Any]):
         state.guard.load_state_dict(d["nonfinite_guard"])
     if getattr(state, "ada", None) is not None and "ada" in d:
         state.ada.load_state_dict(d["ada"])
+    if getattr(state, "lecam", None) is not None and "lecam" in d:
+        state.lecam.load_state_dict(d["lecam"])
     return state.replace(step=int(np.asarray(d["step"])),
                          generator_state={k: xmc_net._tree_to_dev(ops, v) for k, v in d["generator_state"].items()},
                          discriminator_state={k: xmc_net._tree_to_dev(ops, v) for k, v in d["discriminator_state"].items()},

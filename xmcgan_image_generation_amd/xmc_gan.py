@@ -25,6 +25,7 @@ import torch
 from .libml import ada as ada_lib
 from .libml import attention_lib as attn_lib
 from .libml import diff_augment
+from .libml import lecam as lecam_lib
 from .libml import losses
 from .libml import nonfinite_guard
 from .nets import xmc_net
@@ -77,8 +78,10 @@ def clip_guidance_weight(config):
 
 
 def metric_keys(config):
-    """the keys of train_g_d's metrics under ``config``: ``METRIC_KEYS``, and ``c_loss_g_clip`` with the CLIP term on"""
-    return METRIC_KEYS + ((CLIP_METRIC_KEY,) if clip_guidance_weight(config) > 0.0 else ())
+    """the keys of train_g_d's metrics under ``config``: ``METRIC_KEYS``, ``c_loss_g_clip`` with the CLIP term on, and
+    ``d_loss_lecam`` (the unweighted R of train_g_d's half step) with config.lecam_weight"""
+    return (METRIC_KEYS + ((CLIP_METRIC_KEY,) if clip_guidance_weight(config) > 0.0 else ())
+            + ((lecam_lib.METRIC_KEY,) if lecam_lib.enabled(config) else ()))
 
 
 def create_additional_data(config):
@@ -309,6 +312,23 @@ def check_ada_replicas(config, grad_sync):
                          "its own on its own logits, their p would drift apart, and only rank 0's would be checkpointed")
 
 
+def _lecam_of(state, config):
+    """config.lecam_weight -> the state's ``LecamController`` (ValueError when the state was built without one), else None"""
+    if not lecam_lib.enabled(config):
+        return None
+    if getattr(state, "lecam", None) is None:
+        raise ValueError("config.lecam_weight is set but the TrainState has no LecamController (state.lecam): build the state "
+                         "with create_train_state under the same config")
+    return state.lecam
+
+
+def check_lecam_replicas(config, grad_sync):
+    """config.lecam_weight with replicas is an error, the same decision as for config.ada_target"""
+    if grad_sync is not None and lecam_lib.enabled(config):
+        raise ValueError("config.lecam_weight is not supported with replicas (grad_sync): every replica would keep anchors of its "
+                         "own from its own logits, they would drift apart, and only rank 0's would be checkpointed")
+
+
 def _augment_pullback(ops, d_tape, dimg):
     """d g_loss / d generated images from the gradient ``Discriminator.backward_g`` returns (which, under config.diff_augment, is
     the one with respect to the AUGMENTED images): the transpose of the augmentation, on the stream this is called on"""
@@ -418,6 +438,12 @@ def _forward(rng, config, state, batch, g, d, need_g_tape, image_model=None, aft
     b = img.shape[0]
     hinge = ops.zeros((2,))
     dld, dlg = losses.hinge_loss(ops, logit, b, hinge[0:1], hinge[1:2])      # xmc_gan.py:144-145
+    lecam_r = None
+    if _lecam_of(state, config) is not None:
+        # config.lecam_weight (not in the reference): dld takes 2 lambda / b * (logit - anchor) in place, directly behind the hinge
+        # launch on its stream, and the anchors move.  dlg, the hinge slots and d_loss stay as they are.  Forward values only: not
+        # under the non-finite guard's verdict (a batch with a non-finite logit leaves the anchors alone)
+        lecam_r = state.lecam.apply(ops, logit, dld, b)
     if not want_metrics:                     # train_d discards them (xmc_gan.py:238-256 returns the state only)
         out = None
     elif hasattr(ops, "loss_assemble"):      # one launch instead of ten scalar adds in front of the backward pass
@@ -427,6 +453,8 @@ def _forward(rng, config, state, batch, g, d, need_g_tape, image_model=None, aft
         rd = {k: loss_vec[i] for i, k in enumerate(xmc_net.LOSS_SLOTS)}
         c_loss_d, c_loss_g = calculate_contrastive_loss(rd)
         out = dict(d_loss=hinge[0] + c_loss_d, g_loss=hinge[1] + c_loss_g, c_loss_d=c_loss_d, c_loss_g=c_loss_g)
+    if out is not None and lecam_r is not None:
+        out[lecam_lib.METRIC_KEY] = lecam_r[0]       # the UNWEIGHTED R (train_g_d's metrics only: train_d discards them)
     return state, out, dld, dlg, g_tape, d_tape, new_g_stats, new_sn, pre, cpre
 
 
@@ -576,6 +604,7 @@ def train_d(rng, state, batch, generator, discriminator, config, grad_sync=None,
     if hasattr(ops, "begin_pool"):
         ops.begin_pool()
     check_ada_replicas(config, grad_sync)
+    check_lecam_replicas(config, grad_sync)
     state, guard = _guarded(state, config, ops, g, d, grad_sync)
     d_arena = state.d_optimizer.arena
     deferred_in = getattr(state, "pending", None) is not None
@@ -650,6 +679,7 @@ def train_g_d(rng, state, batch, generator, discriminator, config, additional_da
     if hasattr(ops, "begin_pool"):
         ops.begin_pool()
     check_ada_replicas(config, grad_sync)
+    check_lecam_replicas(config, grad_sync)
     state, guard = _guarded(state, config, ops, g, d, grad_sync)
     d_arena, g_arena = state.d_optimizer.arena, state.g_optimizer.arena
     if getattr(state, "pending", None) is None:
