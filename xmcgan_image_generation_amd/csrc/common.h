@@ -27,6 +27,8 @@ static inline int xmc_hip_err(hipError_t e) { return e == hipSuccess ? XMC_OK : 
     do {                  \
         if (!(cond)) return XMC_EINVAL; \
     } while (0)
+// a NULL pointer counts as aligned: an optional buffer is checked with the same expression
+static inline bool xmc_aligned(const void* q, uintptr_t bytes) { return ((uintptr_t)q % bytes) == 0; }
 
 __device__ __forceinline__ float bf2f(bf16_t v) { return __uint_as_float(((uint32_t)v) << 16); }
 // float32 -> bf16, round to nearest even: ONE v_cvt_pk_bf16_f32 per pair (gfx950 has the conversion in hardware;

@@ -1,5 +1,6 @@
 // Streaming pointwise / resampling kernels (HBM-bound; 16-byte vectors, grid-stride) and the
 // fused Adam(+EMA) arena update.
+#include "adam_update.h"
 #include "common.h"
 
 namespace {
@@ -173,7 +174,10 @@ __global__ __launch_bounds__(256) void add_kernel(const T* __restrict__ a, const
 // accumulates into a clean arena without a separate fill).
 // GUARD (config.skip_nonfinite_updates; xmc_*_guarded): verdict[0] != 0 (xmc_nonfinite_verdict found a NaN or an infinity in what
 // this half step would commit) leaves p, m, v and ema as they are; the gradient is still zeroed where zero_g == 1 would zero
-// it, so that the bad values do not reach the next half step.  The GUARD = false instantiation is the kernel as it was.
+// it, so that the bad values do not reach the next half step.  The GUARD = false instantiation is the kernel as it was, and
+// stays so in BITS: the arithmetic of all four instantiations (and of adam_wprep_kernel) is the one definition of adam_update.h,
+// whose roundings are written out and reproduce what the float4 loop computed before (tests/test_gpu_adam_bits.py).  The scalar
+// tail -- never run by the product: ParamArena pads every arena to 64 -- takes the loop's rounding too.
 template <bool FIX, bool GUARD = false>
 __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, float* __restrict__ g,
                                                    float* __restrict__ m, float* __restrict__ v,
@@ -196,16 +200,14 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, float*
         }
     }
     if (corr) { ic1 = corr[1]; ic2 = corr[2]; }      // device-side step counter (hipGraph replay): see adam_advance_kernel
+    const AdamHyper h = {lr, b1, b2, eps, ic1, ic2, gs, d};
     const long long n4 = n >> 2;
     for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n4; i += (long long)gridDim.x * 256) {
         float4 pp = reinterpret_cast<float4*>(p)[i];
         float4 gg = reinterpret_cast<const float4*>(g)[i];
         float4 mm = reinterpret_cast<float4*>(m)[i];
         float4 vv = reinterpret_cast<float4*>(v)[i];
-        float* pf = reinterpret_cast<float*>(&pp);
         float* gf = reinterpret_cast<float*>(&gg);
-        float* mf = reinterpret_cast<float*>(&mm);
-        float* vf = reinterpret_cast<float*>(&vv);
         bool fixed = false;
         if constexpr (!FIX) {
             if (map && map[i >> 4] == -2) continue;  // a tensor the fused optimiser + preparation kernel updates (adam_wprep_kernel)
@@ -225,17 +227,8 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, float*
                     // index u / v past the entry's slices (round-4 advisor finding; no current shape has padding)
                 } else if ((cols & 3u) == 0) {       // a float4 never straddles a row
                     const unsigned r = t / cols, c = t - r * cols;
-                    if (e.u_axis == 0) {
-                        const float ur = uu[r] * k;
-                        const float4 v4 = *reinterpret_cast<const float4*>(vw + c);
-                        gf[0] = (gf[0] - ur * v4.x) * is; gf[1] = (gf[1] - ur * v4.y) * is;
-                        gf[2] = (gf[2] - ur * v4.z) * is; gf[3] = (gf[3] - ur * v4.w) * is;
-                    } else {
-                        const float vr = vw[r] * k;
-                        const float4 u4 = *reinterpret_cast<const float4*>(uu + c);
-                        gf[0] = (gf[0] - vr * u4.x) * is; gf[1] = (gf[1] - vr * u4.y) * is;
-                        gf[2] = (gf[2] - vr * u4.z) * is; gf[3] = (gf[3] - vr * u4.w) * is;
-                    }
+                    if (e.u_axis == 0) sigma_term4(gg, sigma_row_factor(uu[r], k), *reinterpret_cast<const float4*>(vw + c), is);
+                    else sigma_term4(gg, sigma_row_factor(vw[r], k), *reinterpret_cast<const float4*>(uu + c), is);
                 } else {
                     const unsigned total = (unsigned)e.rows * cols;
 #pragma unroll
@@ -243,42 +236,29 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, float*
                         const unsigned tq = t + q;
                         if (tq < total) {            // (the tensor's 64-element padding carries no gradient)
                             const unsigned r = tq / cols, c = tq - r * cols;
-                            const float uv = e.u_axis == 0 ? uu[r] * vw[c] : uu[c] * vw[r];
-                            gf[q] = (gf[q] - k * uv) * is;
+                            gf[q] = e.u_axis == 0 ? sigma_term(gf[q], k, uu[r], vw[c], is) : sigma_term(gf[q], k, uu[c], vw[r], is);
                         }
                     }
                 }
             }
         }
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            const float gr = gf[e] * gs;
-            mf[e] = b1 * mf[e] + (1.f - b1) * gr;
-            vf[e] = b2 * vf[e] + (1.f - b2) * gr * gr;
-            pf[e] -= lr * (mf[e] * ic1) / (sqrtf(vf[e] * ic2) + eps);
-        }
+        adam_update4(pp, gg, mm, vv, h);
         reinterpret_cast<float4*>(p)[i] = pp;
         reinterpret_cast<float4*>(m)[i] = mm;
         reinterpret_cast<float4*>(v)[i] = vv;
-        if (zero_g == 1) reinterpret_cast<float4*>(g)[i] = make_float4(0.f, 0.f, 0.f, 0.f);
-        else if (zero_g == 2 && fixed) reinterpret_cast<float4*>(g)[i] = gg;      // keep the FINAL gradient readable (tests, tools)
+        store_consumed_grad(reinterpret_cast<float4*>(g) + i, gg, zero_g, fixed);
         if (ema) {
             float4 ee = reinterpret_cast<float4*>(ema)[i];
-            float* ef = reinterpret_cast<float*>(&ee);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) ef[e] = ef[e] * d + (1.f - d) * pf[e];
+            ema_mix4(ee, pp, d);
             reinterpret_cast<float4*>(ema)[i] = ee;
         }
     }
     // tail (arena sizes are padded to 64 by the host, kept for safety; never part of a spectral tensor)
     if (blockIdx.x == 0 && threadIdx.x < (n & 3)) {
         const long long i = (n4 << 2) + threadIdx.x;
-        const float gr = g[i] * gs;
-        m[i] = b1 * m[i] + (1.f - b1) * gr;
-        v[i] = b2 * v[i] + (1.f - b2) * gr * gr;
-        p[i] -= lr * (m[i] * ic1) / (sqrtf(v[i] * ic2) + eps);
+        adam_update(p[i], g[i], m[i], v[i], h);
         if (zero_g == 1) g[i] = 0.f;
-        if (ema) ema[i] = ema[i] * d + (1.f - d) * p[i];
+        if (ema) ema[i] = ema_mix(ema[i], p[i], d);
     }
 }
 
@@ -421,19 +401,6 @@ extern "C" int xmc_add(const void* a, const void* b, void* out, int64_t n, int32
     XMC_LAUNCH_RET();
 }
 
-extern "C" int xmc_adam_ema(float* p, const float* g, float* m, float* v, float* ema, int64_t n, float lr,
-                            float beta1, float beta2, float eps, float c1, float c2, float grad_scale,
-                            float ema_decay, void* stream) {
-    XMC_REQUIRE(p && g && m && v && n > 0 && c1 > 0.f && c2 > 0.f);
-    XMC_REQUIRE(((uintptr_t)p % 16) == 0 && ((uintptr_t)g % 16) == 0 && ((uintptr_t)m % 16) == 0 &&
-                ((uintptr_t)v % 16) == 0 && (ema == nullptr || ((uintptr_t)ema % 16) == 0));
-    hipLaunchKernelGGL((adam_kernel<false>), dim3(grid_for(n / 4 + 1)), dim3(256), 0, static_cast<hipStream_t>(stream), p, const_cast<float*>(g),
-                       m, v, ema, (long long)n, lr, beta1, beta2, eps, 1.f / c1, 1.f / c2, grad_scale, ema_decay,
-                       static_cast<const float*>(nullptr), 0, (const short*)nullptr, (const xmc_sn_entry*)nullptr, (const float*)nullptr,
-                       (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, (const int*)nullptr);
-    XMC_LAUNCH_RET();
-}
-
 // step counter of one optimiser kept in DEVICE memory: state[0] = t (int32 bits), state[1] = 1 / (1 - beta1^t),
 // state[2] = 1 / (1 - beta2^t).  One thread advances t and refreshes the two bias corrections in double precision;
 // the Adam kernel launched right behind it reads them -- so a captured hipGraph replays the right step.
@@ -448,19 +415,72 @@ __global__ void adam_advance_kernel(float* state, double b1, double b2, const in
     state[2] = (float)(1.0 / (1.0 - pow(b2, (double)t)));
 }
 
+namespace {
+
+// What the five flat entry points below hand to launch_adam_flat, in the order of their own parameters: an entry point fills the
+// fields it has, the rest keep their defaults (the gradient left alone, no map, no table, no verdict).
+struct AdamFlatArgs {
+    float *p, *g, *m, *v, *ema;
+    int64_t n;
+    float lr;
+    double beta1, beta2;
+    float eps;
+    float* step_state;                               // advanced here, read by the kernel (NULL with host_step)
+    float grad_scale, ema_decay;
+    void* stream;
+    int32_t zero_grads = 0;
+    const void *map = nullptr, *table = nullptr;
+    int32_t n_entries = 0;
+    const float *kvec = nullptr, *scal = nullptr, *u = nullptr, *vv = nullptr;
+    bool guarded = false;
+    const int32_t* verdict = nullptr;
+    bool host_step = false;                          // xmc_adam_ema: the caller computed c = 1 - beta^t
+    float c1 = 1.f, c2 = 1.f;
+};
+
+int validate_adam_flat(const AdamFlatArgs& a) {
+    XMC_REQUIRE(a.p && a.g && a.m && a.v && a.n > 0);
+    XMC_REQUIRE(xmc_aligned(a.p, 16) && xmc_aligned(a.g, 16) && xmc_aligned(a.m, 16) && xmc_aligned(a.v, 16) && xmc_aligned(a.ema, 16));     // (ema may be NULL)
+    XMC_REQUIRE(a.host_step ? (a.c1 > 0.f && a.c2 > 0.f) : a.step_state != nullptr);
+    XMC_REQUIRE(!a.table || (a.map && a.n_entries > 0 && a.kvec && a.scal && a.u && a.vv));     // (map without table: skip marks only)
+    XMC_REQUIRE(!a.guarded || (a.verdict && xmc_aligned(a.verdict, 4)));
+    return XMC_OK;
+}
+
+// adam_kernel<FIX = a table is given, GUARD = the entry point is a guarded one>, behind adam_advance_kernel where the step lives
+// on the device
+int launch_adam_flat(const AdamFlatArgs& a) {
+    if (const int rc = validate_adam_flat(a)) return rc;
+    hipStream_t s = static_cast<hipStream_t>(a.stream);
+    const int* verdict = a.guarded ? static_cast<const int*>(a.verdict) : nullptr;
+    if (!a.host_step)
+        hipLaunchKernelGGL(a.guarded ? adam_advance_kernel<true> : adam_advance_kernel<false>, dim3(1), dim3(1), 0, s, a.step_state,
+                           a.beta1, a.beta2, verdict);
+    const auto kernel = a.table ? (a.guarded ? adam_kernel<true, true> : adam_kernel<true, false>)
+                                : (a.guarded ? adam_kernel<false, true> : adam_kernel<false, false>);
+    hipLaunchKernelGGL(kernel, dim3(grid_for(a.n / 4 + 1)), dim3(256), 0, s, a.p, a.g, a.m, a.v, a.ema, (long long)a.n, a.lr,
+                       (float)a.beta1, (float)a.beta2, a.eps, a.host_step ? 1.f / a.c1 : 1.f, a.host_step ? 1.f / a.c2 : 1.f,
+                       a.grad_scale, a.ema_decay, static_cast<const float*>(a.step_state), a.zero_grads,
+                       static_cast<const short*>(a.map), static_cast<const xmc_sn_entry*>(a.table), a.kvec, a.scal, a.u, a.vv, verdict);
+    XMC_LAUNCH_RET();
+}
+
+}  // namespace
+
+extern "C" int xmc_adam_ema(float* p, const float* g, float* m, float* v, float* ema, int64_t n, float lr,
+                            float beta1, float beta2, float eps, float c1, float c2, float grad_scale,
+                            float ema_decay, void* stream) {
+    AdamFlatArgs a = {p, const_cast<float*>(g), m, v, ema, n, lr, beta1, beta2, eps, nullptr, grad_scale, ema_decay, stream};
+    a.host_step = true;
+    a.c1 = c1;
+    a.c2 = c2;
+    return launch_adam_flat(a);
+}
+
 extern "C" int xmc_adam_ema_dev(float* p, const float* g, float* m, float* v, float* ema, int64_t n, float lr,
                                 double beta1, double beta2, float eps, float* step_state, float grad_scale,
                                 float ema_decay, void* stream) {
-    XMC_REQUIRE(p && g && m && v && n > 0 && step_state);
-    XMC_REQUIRE(((uintptr_t)p % 16) == 0 && ((uintptr_t)g % 16) == 0 && ((uintptr_t)m % 16) == 0 &&
-                ((uintptr_t)v % 16) == 0 && (ema == nullptr || ((uintptr_t)ema % 16) == 0));
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    hipLaunchKernelGGL((adam_advance_kernel<false>), dim3(1), dim3(1), 0, s, step_state, beta1, beta2, (const int*)nullptr);
-    hipLaunchKernelGGL((adam_kernel<false>), dim3(grid_for(n / 4 + 1)), dim3(256), 0, s, p, const_cast<float*>(g), m, v, ema, (long long)n, lr,
-                       (float)beta1, (float)beta2, eps, 1.f, 1.f, grad_scale, ema_decay, static_cast<const float*>(step_state),
-                       0, (const short*)nullptr, (const xmc_sn_entry*)nullptr, (const float*)nullptr, (const float*)nullptr,
-                       (const float*)nullptr, (const float*)nullptr, (const int*)nullptr);
-    XMC_LAUNCH_RET();
+    return launch_adam_flat({p, const_cast<float*>(g), m, v, ema, n, lr, beta1, beta2, eps, step_state, grad_scale, ema_decay, stream});
 }
 
 // xmc_adam_ema_dev with (a) the consumed gradient zeroed in place (zero_grads) and (b) the gradient through sigma of the
@@ -471,23 +491,8 @@ extern "C" int xmc_adam_ema_dev_sn(float* p, float* g, float* m, float* v, float
                                    double beta2, float eps, float* step_state, float grad_scale, float ema_decay,
                                    int32_t zero_grads, const void* map, const void* table, int32_t n_entries,
                                    const float* kvec, const float* scal, const float* u, const float* vv, void* stream) {
-    XMC_REQUIRE(p && g && m && v && n > 0 && step_state);
-    XMC_REQUIRE(((uintptr_t)p % 16) == 0 && ((uintptr_t)g % 16) == 0 && ((uintptr_t)m % 16) == 0 &&
-                ((uintptr_t)v % 16) == 0 && (ema == nullptr || ((uintptr_t)ema % 16) == 0));
-    XMC_REQUIRE(!table || (map && n_entries > 0 && kvec && scal && u && vv));     // (map without table: skip marks only)
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    hipLaunchKernelGGL((adam_advance_kernel<false>), dim3(1), dim3(1), 0, s, step_state, beta1, beta2, (const int*)nullptr);
-    if (table)
-        hipLaunchKernelGGL((adam_kernel<true>), dim3(grid_for(n / 4 + 1)), dim3(256), 0, s, p, g, m, v, ema, (long long)n, lr,
-                           (float)beta1, (float)beta2, eps, 1.f, 1.f, grad_scale, ema_decay, static_cast<const float*>(step_state),
-                           zero_grads, static_cast<const short*>(map), static_cast<const xmc_sn_entry*>(table), kvec, scal, u, vv,
-                           (const int*)nullptr);
-    else
-        hipLaunchKernelGGL((adam_kernel<false>), dim3(grid_for(n / 4 + 1)), dim3(256), 0, s, p, g, m, v, ema, (long long)n, lr,
-                           (float)beta1, (float)beta2, eps, 1.f, 1.f, grad_scale, ema_decay, static_cast<const float*>(step_state),
-                           zero_grads, static_cast<const short*>(map), (const xmc_sn_entry*)nullptr, (const float*)nullptr,
-                           (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, (const int*)nullptr);
-    XMC_LAUNCH_RET();
+    return launch_adam_flat({p, g, m, v, ema, n, lr, beta1, beta2, eps, step_state, grad_scale, ema_decay, stream, zero_grads, map, table,
+                             n_entries, kvec, scal, u, vv});
 }
 
 // ---- config.skip_nonfinite_updates: the guarded forms.  Same arguments as the entry points above plus `verdict` (the int32[4]
@@ -496,16 +501,10 @@ extern "C" int xmc_adam_ema_dev_sn(float* p, float* g, float* m, float* v, float
 extern "C" int xmc_adam_ema_dev_guarded(float* p, const float* g, float* m, float* v, float* ema, int64_t n, float lr, double beta1,
                                         double beta2, float eps, float* step_state, float grad_scale, float ema_decay,
                                         const int32_t* verdict, void* stream) {
-    XMC_REQUIRE(p && g && m && v && n > 0 && step_state && verdict && ((uintptr_t)verdict % 4) == 0);
-    XMC_REQUIRE(((uintptr_t)p % 16) == 0 && ((uintptr_t)g % 16) == 0 && ((uintptr_t)m % 16) == 0 &&
-                ((uintptr_t)v % 16) == 0 && (ema == nullptr || ((uintptr_t)ema % 16) == 0));
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    hipLaunchKernelGGL((adam_advance_kernel<true>), dim3(1), dim3(1), 0, s, step_state, beta1, beta2, static_cast<const int*>(verdict));
-    hipLaunchKernelGGL((adam_kernel<false, true>), dim3(grid_for(n / 4 + 1)), dim3(256), 0, s, p, const_cast<float*>(g), m, v, ema,
-                       (long long)n, lr, (float)beta1, (float)beta2, eps, 1.f, 1.f, grad_scale, ema_decay, static_cast<const float*>(step_state),
-                       0, (const short*)nullptr, (const xmc_sn_entry*)nullptr, (const float*)nullptr, (const float*)nullptr,
-                       (const float*)nullptr, (const float*)nullptr, static_cast<const int*>(verdict));
-    XMC_LAUNCH_RET();
+    AdamFlatArgs a = {p, const_cast<float*>(g), m, v, ema, n, lr, beta1, beta2, eps, step_state, grad_scale, ema_decay, stream};
+    a.guarded = true;
+    a.verdict = verdict;
+    return launch_adam_flat(a);
 }
 
 extern "C" int xmc_adam_ema_dev_sn_guarded(float* p, float* g, float* m, float* v, float* ema, int64_t n, float lr, double beta1,
@@ -513,23 +512,8 @@ extern "C" int xmc_adam_ema_dev_sn_guarded(float* p, float* g, float* m, float* 
                                            int32_t zero_grads, const void* map, const void* table, int32_t n_entries,
                                            const float* kvec, const float* scal, const float* u, const float* vv,
                                            const int32_t* verdict, void* stream) {
-    XMC_REQUIRE(p && g && m && v && n > 0 && step_state && verdict && ((uintptr_t)verdict % 4) == 0);
-    XMC_REQUIRE(((uintptr_t)p % 16) == 0 && ((uintptr_t)g % 16) == 0 && ((uintptr_t)m % 16) == 0 &&
-                ((uintptr_t)v % 16) == 0 && (ema == nullptr || ((uintptr_t)ema % 16) == 0));
-    XMC_REQUIRE(!table || (map && n_entries > 0 && kvec && scal && u && vv));     // (map without table: skip marks only)
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    hipLaunchKernelGGL((adam_advance_kernel<true>), dim3(1), dim3(1), 0, s, step_state, beta1, beta2, static_cast<const int*>(verdict));
-    if (table)
-        hipLaunchKernelGGL((adam_kernel<true, true>), dim3(grid_for(n / 4 + 1)), dim3(256), 0, s, p, g, m, v, ema, (long long)n, lr,
-                           (float)beta1, (float)beta2, eps, 1.f, 1.f, grad_scale, ema_decay, static_cast<const float*>(step_state),
-                           zero_grads, static_cast<const short*>(map), static_cast<const xmc_sn_entry*>(table), kvec, scal, u, vv,
-                           static_cast<const int*>(verdict));
-    else
-        hipLaunchKernelGGL((adam_kernel<false, true>), dim3(grid_for(n / 4 + 1)), dim3(256), 0, s, p, g, m, v, ema, (long long)n, lr,
-                           (float)beta1, (float)beta2, eps, 1.f, 1.f, grad_scale, ema_decay, static_cast<const float*>(step_state),
-                           zero_grads, static_cast<const short*>(map), (const xmc_sn_entry*)nullptr, (const float*)nullptr,
-                           (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, static_cast<const int*>(verdict));
-    XMC_LAUNCH_RET();
+    return launch_adam_flat({p, g, m, v, ema, n, lr, beta1, beta2, eps, step_state, grad_scale, ema_decay, stream, zero_grads, map, table,
+                             n_entries, kvec, scal, u, vv, true, verdict});
 }
 
 // Running sums of a step's scalar metrics, kept on the device so that a replayed training graph needs no host read per step

@@ -15,6 +15,7 @@
 //   B1  dot_i = <G_i, W_i>        B2  G_i <- (G_i - dot_i * inv_i * outer(u_i, v_i)) * inv_i
 // Work is split into fixed-size chunks; a workgroup finds its (weight, chunk) with a linear scan of
 // the <= 64-entry prefix table.
+#include "adam_update.h"
 #include "common.h"
 
 namespace {
@@ -531,13 +532,13 @@ __global__ __launch_bounds__(256) void adam_wprep_kernel(const WprepEntry* __res
             return;
         }
     }
-    const float ic1 = corr[1], ic2 = corr[2];        // device-side step counter, already advanced (adam_advance_kernel)
+    const AdamHyper h = {lr, b1, b2, eps, corr[1], corr[2], gs, d};      // device-side step counter, already advanced (adam_advance_kernel)
     const bool spectral = FIX && (e.flags & 16);
     float ur = 0.f, is = 1.f;
     if (spectral) {
         const int ent = e.flags >> 8;                // index of this weight in the spectral bank (kvec / scal)
         is = scal[2 * ent + 1];
-        ur = uvec[e.u_off + n0 + row] * kvec[ent];
+        ur = sigma_row_factor(uvec[e.u_off + n0 + row], kvec[ent]);
         if (tid < 32) us[tid] = uvec[e.u_off + n0 + tid];
     }
     const size_t base = (size_t)e.w_off + (size_t)(n0 + row) * taps * cin + c0 + c4;
@@ -560,33 +561,17 @@ __global__ __launch_bounds__(256) void adam_wprep_kernel(const WprepEntry* __res
             const int tap = t0 + k;
             if (tap >= taps) break;
             const size_t o = base + (size_t)tap * cin;
-            float* pf = reinterpret_cast<float*>(&pp[k]);
-            float* gf = reinterpret_cast<float*>(&gg[k]);
-            float* mf = reinterpret_cast<float*>(&mm[k]);
-            float* vf = reinterpret_cast<float*>(&vv[k]);
-            if (spectral) {
-                gf[0] = (gf[0] - ur * v4[k].x) * is; gf[1] = (gf[1] - ur * v4[k].y) * is;
-                gf[2] = (gf[2] - ur * v4[k].z) * is; gf[3] = (gf[3] - ur * v4[k].w) * is;
-            }
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const float gr = gf[q] * gs;
-                mf[q] = b1 * mf[q] + (1.f - b1) * gr;
-                vf[q] = b2 * vf[q] + (1.f - b2) * gr * gr;
-                pf[q] -= lr * (mf[q] * ic1) / (sqrtf(vf[q] * ic2) + eps);
-            }
+            if (spectral) sigma_term4(gg[k], ur, v4[k], is);
+            adam_update4(pp[k], gg[k], mm[k], vv[k], h);
             *reinterpret_cast<float4*>(p + o) = pp[k];
             *reinterpret_cast<float4*>(m + o) = mm[k];
             *reinterpret_cast<float4*>(v + o) = vv[k];
-            if (zero_g == 1) *reinterpret_cast<float4*>(g + o) = make_float4(0.f, 0.f, 0.f, 0.f);
-            else if (zero_g == 2 && spectral) *reinterpret_cast<float4*>(g + o) = gg[k];
+            store_consumed_grad(reinterpret_cast<float4*>(g + o), gg[k], zero_g, spectral);
             if (ema) {
-                float* ef = reinterpret_cast<float*>(&ee[k]);
-#pragma unroll
-                for (int q = 0; q < 4; ++q) ef[q] = ef[q] * d + (1.f - d) * pf[q];
+                ema_mix4(ee[k], pp[k], d);
                 *reinterpret_cast<float4*>(ema + o) = ee[k];
             }
-            t9[tap][row][c4] = pf[0]; t9[tap][row][c4 + 1] = pf[1]; t9[tap][row][c4 + 2] = pf[2]; t9[tap][row][c4 + 3] = pf[3];
+            t9[tap][row][c4] = pp[k].x; t9[tap][row][c4 + 1] = pp[k].y; t9[tap][row][c4 + 2] = pp[k].z; t9[tap][row][c4 + 3] = pp[k].w;
         }
     }
     __syncthreads();
@@ -694,6 +679,51 @@ extern "C" int xmc_wprep_batched(const void* table, int32_t n, const float* para
     XMC_LAUNCH_RET();
 }
 
+namespace {
+
+// What the two tile entry points below hand to launch_adam_tiles, in the order of their own parameters
+struct AdamTilesArgs {
+    const void* table;
+    int32_t n, blocks;
+    float *p, *g, *m, *v, *ema;
+    float lr;
+    double beta1, beta2;
+    float eps;
+    const float* step_state;
+    float grad_scale, ema_decay;
+    int32_t zero_grads;
+    const float *kvec, *scal, *u, *vv;
+    void *wf_buf, *wd_buf, *pf_buf, *pd_buf;
+    float* part;
+    void* stream;
+    bool guarded = false;
+    const int32_t* verdict = nullptr;
+};
+
+int validate_adam_tiles(const AdamTilesArgs& a) {
+    XMC_REQUIRE(a.table && a.p && a.g && a.m && a.v && a.step_state && a.n > 0 && a.n <= 64 && a.blocks > 0);
+    XMC_REQUIRE(sizeof(WprepEntry) == sizeof(xmc_wprep_entry));
+    XMC_REQUIRE(xmc_aligned(a.p, 16) && xmc_aligned(a.g, 16) && xmc_aligned(a.m, 16) && xmc_aligned(a.v, 16) && xmc_aligned(a.ema, 16));     // (ema may be NULL)
+    XMC_REQUIRE(!a.kvec || (a.scal && a.u && a.vv && a.part && xmc_aligned(a.vv, 16)));
+    XMC_REQUIRE(!a.guarded || (a.verdict && xmc_aligned(a.verdict, 4)));
+    return XMC_OK;
+}
+
+// adam_wprep_kernel<FIX = kvec is given, GUARD = the entry point is the guarded one>
+int launch_adam_tiles(const AdamTilesArgs& a) {
+    if (const int rc = validate_adam_tiles(a)) return rc;
+    const auto kernel = a.kvec ? (a.guarded ? adam_wprep_kernel<true, true> : adam_wprep_kernel<true, false>)
+                               : (a.guarded ? adam_wprep_kernel<false, true> : adam_wprep_kernel<false, false>);
+    hipLaunchKernelGGL(kernel, dim3(a.blocks), dim3(256), 0, static_cast<hipStream_t>(a.stream), static_cast<const WprepEntry*>(a.table),
+                       a.n, a.p, a.g, a.m, a.v, a.ema, a.lr, (float)a.beta1, (float)a.beta2, a.eps, a.step_state, a.grad_scale,
+                       a.ema_decay, a.zero_grads, a.kvec, a.scal, a.u, a.vv, static_cast<bf16_t*>(a.wf_buf),
+                       static_cast<bf16_t*>(a.wd_buf), static_cast<bf16_t*>(a.pf_buf), static_cast<bf16_t*>(a.pd_buf), a.part,
+                       a.guarded ? static_cast<const int*>(a.verdict) : nullptr);
+    XMC_LAUNCH_RET();
+}
+
+}  // namespace
+
 // The Adam (+ EMA) update of the `table` weights fused with their preparation (adam_wprep_kernel).  `step_state` must ALREADY be
 // advanced for this update: call xmc_adam_ema_dev_sn on the same arena first -- with a map that carries -2 on these tensors,
 // so that the flat kernel leaves them alone -- then this.  kvec / scal / u / vv (spectral arenas: the gradient through sigma of
@@ -704,24 +734,8 @@ extern "C" int xmc_adam_wprep_tiles(const void* table, int32_t n, int32_t blocks
                                     float ema_decay, int32_t zero_grads, const float* kvec, const float* scal, const float* u,
                                     const float* vv, void* wf_buf, void* wd_buf, void* pf_buf, void* pd_buf, float* part,
                                     void* stream) {
-    XMC_REQUIRE(table && p && g && m && v && step_state && n > 0 && n <= 64 && blocks > 0);
-    XMC_REQUIRE(sizeof(WprepEntry) == sizeof(xmc_wprep_entry));
-    XMC_REQUIRE(((uintptr_t)p % 16) == 0 && ((uintptr_t)g % 16) == 0 && ((uintptr_t)m % 16) == 0 && ((uintptr_t)v % 16) == 0 &&
-                (ema == nullptr || ((uintptr_t)ema % 16) == 0));
-    const bool fix = kvec != nullptr;
-    XMC_REQUIRE(!fix || (scal && u && vv && part && ((uintptr_t)vv % 16) == 0));
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const WprepEntry* tab = static_cast<const WprepEntry*>(table);
-    if (fix)
-        hipLaunchKernelGGL((adam_wprep_kernel<true>), dim3(blocks), dim3(256), 0, s, tab, n, p, g, m, v, ema, lr, (float)beta1, (float)beta2,
-                           eps, step_state, grad_scale, ema_decay, zero_grads, kvec, scal, u, vv, static_cast<bf16_t*>(wf_buf),
-                           static_cast<bf16_t*>(wd_buf), static_cast<bf16_t*>(pf_buf), static_cast<bf16_t*>(pd_buf), part, (const int*)nullptr);
-    else
-        hipLaunchKernelGGL((adam_wprep_kernel<false>), dim3(blocks), dim3(256), 0, s, tab, n, p, g, m, v, ema, lr, (float)beta1, (float)beta2,
-                           eps, step_state, grad_scale, ema_decay, zero_grads, (const float*)nullptr, (const float*)nullptr,
-                           (const float*)nullptr, (const float*)nullptr, static_cast<bf16_t*>(wf_buf), static_cast<bf16_t*>(wd_buf),
-                           static_cast<bf16_t*>(pf_buf), static_cast<bf16_t*>(pd_buf), part, (const int*)nullptr);
-    XMC_LAUNCH_RET();
+    return launch_adam_tiles({table, n, blocks, p, g, m, v, ema, lr, beta1, beta2, eps, step_state, grad_scale, ema_decay, zero_grads,
+                              kvec, scal, u, vv, wf_buf, wd_buf, pf_buf, pd_buf, part, stream});
 }
 
 // xmc_adam_wprep_tiles under config.skip_nonfinite_updates: `verdict` is the int32[4] of xmc_nonfinite_verdict (device memory)
@@ -730,25 +744,8 @@ extern "C" int xmc_adam_wprep_tiles_guarded(const void* table, int32_t n, int32_
                                             float grad_scale, float ema_decay, int32_t zero_grads, const float* kvec, const float* scal,
                                             const float* u, const float* vv, void* wf_buf, void* wd_buf, void* pf_buf, void* pd_buf,
                                             float* part, const int32_t* verdict, void* stream) {
-    XMC_REQUIRE(table && p && g && m && v && step_state && n > 0 && n <= 64 && blocks > 0 && verdict && ((uintptr_t)verdict % 4) == 0);
-    XMC_REQUIRE(sizeof(WprepEntry) == sizeof(xmc_wprep_entry));
-    XMC_REQUIRE(((uintptr_t)p % 16) == 0 && ((uintptr_t)g % 16) == 0 && ((uintptr_t)m % 16) == 0 && ((uintptr_t)v % 16) == 0 &&
-                (ema == nullptr || ((uintptr_t)ema % 16) == 0));
-    const bool fix = kvec != nullptr;
-    XMC_REQUIRE(!fix || (scal && u && vv && part && ((uintptr_t)vv % 16) == 0));
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const WprepEntry* tab = static_cast<const WprepEntry*>(table);
-    const int* vd = static_cast<const int*>(verdict);
-    if (fix)
-        hipLaunchKernelGGL((adam_wprep_kernel<true, true>), dim3(blocks), dim3(256), 0, s, tab, n, p, g, m, v, ema, lr, (float)beta1,
-                           (float)beta2, eps, step_state, grad_scale, ema_decay, zero_grads, kvec, scal, u, vv, static_cast<bf16_t*>(wf_buf),
-                           static_cast<bf16_t*>(wd_buf), static_cast<bf16_t*>(pf_buf), static_cast<bf16_t*>(pd_buf), part, vd);
-    else
-        hipLaunchKernelGGL((adam_wprep_kernel<false, true>), dim3(blocks), dim3(256), 0, s, tab, n, p, g, m, v, ema, lr, (float)beta1,
-                           (float)beta2, eps, step_state, grad_scale, ema_decay, zero_grads, (const float*)nullptr, (const float*)nullptr,
-                           (const float*)nullptr, (const float*)nullptr, static_cast<bf16_t*>(wf_buf), static_cast<bf16_t*>(wd_buf),
-                           static_cast<bf16_t*>(pf_buf), static_cast<bf16_t*>(pd_buf), part, vd);
-    XMC_LAUNCH_RET();
+    return launch_adam_tiles({table, n, blocks, p, g, m, v, ema, lr, beta1, beta2, eps, step_state, grad_scale, ema_decay, zero_grads,
+                              kvec, scal, u, vv, wf_buf, wd_buf, pf_buf, pd_buf, part, stream, true, verdict});
 }
 
 // Power iteration whose first matvec arrives as partial rows from xmc_wprep_batched for the `wtab` entries (`part`); the

@@ -1606,64 +1606,56 @@ class HipOps:
             m[e["w_off"] // align:(e["w_off"] + e["cout"] * e["taps"] * e["cin"]) // align] = -2
         return m.to(self.device)
 
+    def _adam(self, name, *args, verdict=None):
+        """The one call site of the optimiser entry points: ``name(*args, stream)`` or, with a ``verdict``
+        (config.skip_nonfinite_updates), its ``_guarded`` form, which takes the verdict in front of the stream"""
+        if verdict is not None:
+            name, args = name + "_guarded", (*args, _p(verdict))
+        check(getattr(self.lib, name)(*args, self._stream()), name)
+
+    def _zero_g(self, zero_grads):
+        """the kernels' zero_g argument -- 0: the consumed gradient stays, 1: it is zeroed, 2 (``keep_grads``): the FINAL gradient
+        is written back"""
+        return 2 if self.keep_grads else int(bool(zero_grads))
+
     def adam_wprep(self, wp, out, p, g, m, v, ema, step_state, *, lr, beta1, beta2, eps=1e-8, grad_scale=1.0, ema_decay=0.0,
                    zero_grads=True, fix=None, verdict=None):
         """xmc_adam_wprep_tiles: the Adam (+ EMA) update of ``wp``'s weights fused with their preparation into ``out`` = (bufs,
         part); ``step_state`` already advanced by ``adam_ema_dev_sn`` on the same arena (whose map skipped these tensors).
         ``fix`` = (kvec, scal, u, v) for a spectral arena.  ``verdict`` (config.skip_nonfinite_updates): the guarded form."""
         bufs, part = out
-        fa = tuple(_p(t) for t in fix) if fix is not None else (None, None, None, None)
-        if verdict is not None:
-            check(self.lib.xmc_adam_wprep_tiles_guarded(_p(wp["tab"]), wp["n"], wp["blocks"], _p(p), _p(g), _p(m), _p(v), _p(ema), lr, beta1,
-                                                        beta2, eps, _p(step_state), grad_scale, ema_decay,
-                                                        2 if self.keep_grads else int(bool(zero_grads)), *fa, *[_p(b) for b in bufs],
-                                                        _p(part), _p(verdict), self._stream()), "xmc_adam_wprep_tiles_guarded")
-            return
-        check(self.lib.xmc_adam_wprep_tiles(_p(wp["tab"]), wp["n"], wp["blocks"], _p(p), _p(g), _p(m), _p(v), _p(ema), lr, beta1, beta2,
-                                            eps, _p(step_state), grad_scale, ema_decay, 2 if self.keep_grads else int(bool(zero_grads)),
-                                            *fa, *[_p(b) for b in bufs], _p(part), self._stream()), "xmc_adam_wprep_tiles")
+        self._adam("xmc_adam_wprep_tiles", _p(wp["tab"]), wp["n"], wp["blocks"], _p(p), _p(g), _p(m), _p(v), _p(ema), lr, beta1, beta2, eps,
+                   _p(step_state), grad_scale, ema_decay, self._zero_g(zero_grads), *[_p(t) for t in (fix or (None,) * 4)],
+                   *[_p(b) for b in bufs], _p(part), verdict=verdict)
 
     def adam_ema_dev_sn(self, p, g, m, v, ema, step_state, *, lr, beta1, beta2, eps=1e-8, grad_scale=1.0, ema_decay=0.0,
                         zero_grads=True, fix=None, skip_map=None, verdict=None):
         """adam_ema_dev that zeroes the consumed gradient in place and, with ``fix`` = (map, bank, kvec, scal, u, v), applies the
         gradient through sigma on the fly; ``skip_map`` (no ``fix``): tensors marked -2 are left alone (``adam_wprep``).
-        ``verdict`` (config.skip_nonfinite_updates): the guarded form -- verdict[0] != 0 leaves everything but the gradient alone"""
+        ``verdict`` (config.skip_nonfinite_updates): the guarded form -- verdict[0] != 0 leaves everything but the gradient alone.
+        Returns True where the gradient arena is all zeros again."""
         assert step_state.dtype == torch.float32 and step_state.numel() >= 4
         if fix is not None:
             mp, bank, kvec, scal, u, vv = fix
-            args = (_p(mp), _p(bank["tab_fix"]), bank["n"], _p(kvec), _p(scal), _p(u), _p(vv))
-        elif skip_map is not None:
-            args = (_p(skip_map), None, 0, None, None, None, None)
+            sn = (_p(mp), _p(bank["tab_fix"]), bank["n"], _p(kvec), _p(scal), _p(u), _p(vv))
         else:
-            args = (None, None, 0, None, None, None, None)
-        if verdict is not None:
-            check(self.lib.xmc_adam_ema_dev_sn_guarded(_p(p), _p(g), _p(m), _p(v), _p(ema), p.numel(), lr, beta1, beta2, eps,
-                                                       _p(step_state), grad_scale, ema_decay,
-                                                       2 if self.keep_grads else int(bool(zero_grads)), *args, _p(verdict),
-                                                       self._stream()), "xmc_adam_ema_dev_sn_guarded")
-            return not self.keep_grads and bool(zero_grads)
-        check(self.lib.xmc_adam_ema_dev_sn(_p(p), _p(g), _p(m), _p(v), _p(ema), p.numel(), lr, beta1, beta2, eps, _p(step_state),
-                                           grad_scale, ema_decay, 2 if self.keep_grads else int(bool(zero_grads)), *args, self._stream()),
-              "xmc_adam_ema_dev_sn")
-        return not self.keep_grads and bool(zero_grads)        # True: the gradient arena is all zeros again
+            sn = (_p(skip_map), None, 0, None, None, None, None)
+        zero_g = self._zero_g(zero_grads)
+        self._adam("xmc_adam_ema_dev_sn", _p(p), _p(g), _p(m), _p(v), _p(ema), p.numel(), lr, beta1, beta2, eps, _p(step_state),
+                   grad_scale, ema_decay, zero_g, *sn, verdict=verdict)
+        return zero_g == 1
 
     # ---------------------------------------------------------------------------------- optimiser
     def adam_ema(self, p, g, m, v, ema, *, lr, beta1, beta2, step, eps=1e-8, grad_scale=1.0, ema_decay=0.0):
         c1, c2 = 1.0 - beta1 ** step, 1.0 - beta2 ** step
-        check(self.lib.xmc_adam_ema(_p(p), _p(g), _p(m), _p(v), _p(ema), p.numel(), lr, beta1, beta2, eps, c1, c2,
-                                    grad_scale, ema_decay, self._stream()), "xmc_adam_ema")
+        self._adam("xmc_adam_ema", _p(p), _p(g), _p(m), _p(v), _p(ema), p.numel(), lr, beta1, beta2, eps, c1, c2, grad_scale, ema_decay)
 
     def adam_ema_dev(self, p, g, m, v, ema, step_state, *, lr, beta1, beta2, eps=1e-8, grad_scale=1.0, ema_decay=0.0, verdict=None):
         """Adam (+EMA) with the step counter / bias corrections in device memory (``step_state``, 4 float32 slots;
         advanced by one per call) -- the form a captured hipGraph can replay.  ``verdict``: the guarded form."""
         assert step_state.dtype == torch.float32 and step_state.numel() >= 4
-        if verdict is not None:
-            check(self.lib.xmc_adam_ema_dev_guarded(_p(p), _p(g), _p(m), _p(v), _p(ema), p.numel(), lr, beta1, beta2, eps,
-                                                    _p(step_state), grad_scale, ema_decay, _p(verdict), self._stream()),
-                  "xmc_adam_ema_dev_guarded")
-            return
-        check(self.lib.xmc_adam_ema_dev(_p(p), _p(g), _p(m), _p(v), _p(ema), p.numel(), lr, beta1, beta2, eps,
-                                        _p(step_state), grad_scale, ema_decay, self._stream()), "xmc_adam_ema_dev")
+        self._adam("xmc_adam_ema_dev", _p(p), _p(g), _p(m), _p(v), _p(ema), p.numel(), lr, beta1, beta2, eps, _p(step_state), grad_scale,
+                   ema_decay, verdict=verdict)
 
     # ------------------------------------------------------- frozen ResNet-50 feature path (canvases)
     def resize_to_canvas(self, x, hd, hc):
