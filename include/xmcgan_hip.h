@@ -1105,6 +1105,40 @@ int xmc_ada_update(const float* logit, int32_t b, double* state, double target, 
 int xmc_lecam(const float* logit, float* dld, int32_t b, double* state, float* loss, double lam, double decay, int32_t start,
               int32_t one_sided, void* stream);
 
+/* ---- the three controllers with data-parallel replicas (dp.GradSync(schedule="exclusive").gather_rows; the specifications are
+ *      libml/ada.update_rows, libml/lecam.step_rows and libml/nonfinite_guard.merge_rows) ----
+ * XMC_ABI_VERSION stays 36: this section only ADDS entry points, as the two sections above did.
+ * Each rank contributes one small row, the rows are all-gathered in rank order, and every rank runs the same single-workgroup
+ * kernel over the same rows[w][...]: the same bits everywhere, whatever the backend of the exchange.  No atomics, plain vector
+ * stores, no host read.  `state`, `verdict` and `counters` are the buffers of the sections above.
+ *  - xmc_ada_update_rows: rows[w][2b] are the ranks' float32 logit vectors [real; fake]; xmc_ada_update over the concatenation of
+ *    the real halves rows[r][0 .. b), r = 0 .. w - 1 (the generated halves are not read): the same integer counts, then the same
+ *    IEEE double tail.  images_to_full counts GLOBAL images.  w = 1: bit-equal to xmc_ada_update.  Writes state[0 .. 6), nothing else.
+ *    Domain: 1 <= w, 1 <= b, w * 2 b <= 2147483647, 1 <= interval, images_to_full > 0, p_max >= 0, target not NaN; rows 4-byte
+ *    and state 8-byte aligned.
+ *  - xmc_lecam_rows: steps 1 - 4 of xmc_lecam with X_R / X_F = the concatenation, in rank order, of the real halves
+ *    rows[r][0 .. b) / the generated halves rows[r][b .. 2b) (w b elements each; S runs over them in that order):
+ *    R = (S(dr^2) + S(df^2)) / (w b), m_R = S(X_R) / (w b), m_F = S(X_F) / (w b), and "all finite" is tested over all w * 2 b logits
+ *    -- so loss[0] and state are identical on every rank.  dld[0 .. 2b) is THIS rank's gradient: dld_i = float32(double(dld_i) +
+ *    c d_i) with c = (2 lam) / b, the LOCAL b, and d_i from row `rank` (the optimiser's 1 / w gradient scale makes the sum over the
+ *    ranks the gradient of lam R).  The same canonical quiet NaN; no multiply fused with an add.  w = 1: bit-equal to xmc_lecam.
+ *    Writes dld[0 .. 2b), loss[0], state[0 .. 5), nothing else.
+ *    Domain: 1 <= w, 0 <= rank < w, 1 <= b, w * 2 b <= 2147483647; lam finite and >= 0; 0 <= decay < 1; start >= 0; one_sided 0 or
+ *    1; rows, dld and loss 4-byte, state 8-byte aligned.
+ *  - xmc_verdict_merge: rows[w][4] are the ranks' LOCAL verdicts (xmc_nonfinite_verdict into a local row and scratch counters).
+ *    With r* = the lowest r whose rows[r][0] != 0:
+ *        verdict[0] = 1 if there is an r*, else 0;   verdict[1] = min(sum of rows[r][1] in int64, 2147483647);
+ *        verdict[2] = rows[r*][2], or -1;   verdict[3] = r*, or 0
+ *    and the persistent counters[4] advance from the merged verdict[0] by the rule of xmc_nonfinite_verdict.  w = 1 reproduces
+ *    the local verdict.  Writes verdict[0 .. 4) and counters[0 .. 3), nothing else.
+ *    Domain: 1 <= w, 4 w <= 2147483647; all three pointers 4-byte aligned.
+ * Anything else returns XMC_EINVAL and launches nothing. */
+int xmc_ada_update_rows(const float* rows, int32_t w, int32_t b, double* state, double target, double images_to_full,
+                        int32_t interval, double p_max, void* stream);
+int xmc_lecam_rows(const float* rows, int32_t w, int32_t rank, float* dld, int32_t b, double* state, float* loss, double lam,
+                   double decay, int32_t start, int32_t one_sided, void* stream);
+int xmc_verdict_merge(const int32_t* rows, int32_t w, int32_t* verdict, int32_t* counters, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -237,6 +237,9 @@ SIGNATURES = {
     "xmc_ada_gate": [_P, _P, _P, _P, _I, _P],
     "xmc_ada_update": [_P, _I, _P, C.c_double, C.c_double, _I, C.c_double, _P],
     "xmc_lecam": [_P, _P, _I, _P, _P, C.c_double, C.c_double, _I, _I, _P],
+    "xmc_ada_update_rows": [_P, _I, _I, _P, C.c_double, C.c_double, _I, C.c_double, _P],
+    "xmc_lecam_rows": [_P, _I, _I, _P, _I, _P, _P, C.c_double, C.c_double, _I, _I, _P],
+    "xmc_verdict_merge": [_P, _I, _P, _P, _P],
 }
 
 # diagnostic probes: include/xmc_probe.h, libxmc_probe.so (csrc_probe/) -- outside the product ABI

@@ -2,6 +2,8 @@
 //   xmc_ada_gate   -- the plan rows config.diff_augment applies in this half step: part g of a row keeps the drawn values iff
 //                     its uniform is below p, which the kernel reads from the controller's state in device memory
 //   xmc_ada_update -- the controller: counts the signs of D's real logits and, every `interval` half steps, moves p
+//   xmc_ada_update_rows -- the controller with data-parallel replicas: the same update over the real halves of
+//                     the all-gathered logit rows of every rank, so that every rank computes the same p
 // Plain kernel launches on the caller's stream: a captured training step replays them, and the host never reads p.
 // Both are exact (a select, integer counts, IEEE double arithmetic in a fixed order): bit-equal to the specification.
 #include "common.h"
@@ -40,13 +42,19 @@ __global__ __launch_bounds__(ADA_THREADS) void ada_gate_kernel(const float4* __r
 // ----------------------------------------------------------------------------------------------------- xmc_ada_update
 // One workgroup.  The three counts are integers: any reduction order gives the same bits.  Waves reduce with cross-lane moves,
 // the four waves are added in index order through LDS, and lane 0 does the float64 tail.  No atomics.
-__global__ __launch_bounds__(ADA_THREADS) void ada_update_kernel(const uint32_t* __restrict__ logit, int b, double* __restrict__ state,
-                                                                 double target, double images_to_full, int interval, double p_max) {
+// ROWS: `logit` is rows[w][2b] and the real halves rows[r][0 .. b) of all w rows are counted (n = w b <= 2^30 logits: the counts
+// fit an int).  Without ROWS w is not read: one row.
+template <bool ROWS>
+__global__ __launch_bounds__(ADA_THREADS) void ada_update_kernel(const uint32_t* __restrict__ logit, int w, int b,
+                                                                 double* __restrict__ state, double target, double images_to_full,
+                                                                 int interval, double p_max) {
     __shared__ int s_pos[ADA_WAVES], s_neg[ADA_WAVES], s_fin[ADA_WAVES];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int n = ROWS ? w * b : b;
     int pos = 0, neg = 0, fin = 0;
-    for (int i = tid; i < b; i += ADA_THREADS) {         // the first b entries: the real half
-        const uint32_t x = logit[i];
+    for (int k = tid; k < n; k += ADA_THREADS) {         // the first b entries of a row: the real half
+        const int r = ROWS ? k / b : 0;
+        const uint32_t x = logit[(long long)r * 2 * b + (k - r * b)];
         const uint32_t mag = x & 0x7fffffffu;
         const int finite = mag < 0x7f800000u;            // exponent bits not all ones
         const int nonzero = finite && mag != 0u;         // (+-0 counts with sign 0; a denormal has a sign)
@@ -112,7 +120,17 @@ extern "C" int xmc_ada_update(const float* logit, int32_t b, double* state, doub
     XMC_REQUIRE(logit && state && b >= 1 && interval >= 1);
     XMC_REQUIRE(((uintptr_t)logit % 4) == 0 && ((uintptr_t)state % 8) == 0);
     XMC_REQUIRE(target == target && images_to_full > 0.0 && p_max >= 0.0);
-    hipLaunchKernelGGL(ada_update_kernel, dim3(1), dim3(ADA_THREADS), 0, static_cast<hipStream_t>(stream),
-                       reinterpret_cast<const uint32_t*>(logit), (int)b, state, target, images_to_full, (int)interval, p_max);
+    hipLaunchKernelGGL((ada_update_kernel<false>), dim3(1), dim3(ADA_THREADS), 0, static_cast<hipStream_t>(stream),
+                       reinterpret_cast<const uint32_t*>(logit), 1, (int)b, state, target, images_to_full, (int)interval, p_max);
+    XMC_LAUNCH_RET();
+}
+
+extern "C" int xmc_ada_update_rows(const float* rows, int32_t w, int32_t b, double* state, double target, double images_to_full,
+                                   int32_t interval, double p_max, void* stream) {
+    XMC_REQUIRE(rows && state && w >= 1 && b >= 1 && interval >= 1 && (int64_t)w * 2 * (int64_t)b <= 2147483647LL);
+    XMC_REQUIRE(((uintptr_t)rows % 4) == 0 && ((uintptr_t)state % 8) == 0);
+    XMC_REQUIRE(target == target && images_to_full > 0.0 && p_max >= 0.0);
+    hipLaunchKernelGGL((ada_update_kernel<true>), dim3(1), dim3(ADA_THREADS), 0, static_cast<hipStream_t>(stream),
+                       reinterpret_cast<const uint32_t*>(rows), (int)w, (int)b, state, target, images_to_full, (int)interval, p_max);
     XMC_LAUNCH_RET();
 }

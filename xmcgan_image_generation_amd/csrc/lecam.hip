@@ -26,21 +26,29 @@ __device__ __forceinline__ double lecam_tree(double* v, int tid) {
 
 // One workgroup.  Every lane reads the state before the first barrier; lane 0 writes it behind the last.  Element i of dld has one
 // writer (lane i % 256).  No atomics.
-__global__ __launch_bounds__(LECAM_THREADS) void lecam_kernel(const float* __restrict__ logit, float* __restrict__ dld, int b,
-                                                              double* __restrict__ state, float* __restrict__ loss, double lam,
-                                                              double decay, int start, int one_sided) {
+// ROWS: `logit` is rows[w][2b]; X_R / X_F are the real / generated halves of all rows in rank order, n = w b elements each
+// (element k = element k % b of row k / b), and only the elements of row `rank` have a slot in dld.  Without ROWS w and rank
+// are not read: one row, n = b.
+template <bool ROWS>
+__global__ __launch_bounds__(LECAM_THREADS) void lecam_kernel(const float* __restrict__ logit, int w, int rank,
+                                                              float* __restrict__ dld, int b, double* __restrict__ state,
+                                                              float* __restrict__ loss, double lam, double decay, int start,
+                                                              int one_sided) {
 #pragma clang fp contract(off)
     __shared__ double s_rr[LECAM_THREADS], s_ff[LECAM_THREADS], s_r[LECAM_THREADS], s_f[LECAM_THREADS];
     __shared__ int s_bad[LECAM_THREADS];
     const int tid = threadIdx.x;
     const double a_r = state[0], a_f = state[1], ticks = state[2], updates = state[4];
-    const double bb = (double)b;
+    const int n = ROWS ? w * b : b;
+    const double bb = (double)b, nn = (double)n;
     const bool warm = ticks < (double)start || updates == 0.0;   // (= not active: ticks >= start and updates > 0)
     const double c = (2.0 * lam) / bb;
     double rr = 0.0, ff = 0.0, sr = 0.0, sf = 0.0;
     int bad = 0;
-    for (int i = tid; i < b; i += LECAM_THREADS) {
-        const float xr = logit[i], xf = logit[b + i];
+    for (int k = tid; k < n; k += LECAM_THREADS) {
+        const int r = ROWS ? k / b : 0, i = ROWS ? k - r * b : k;
+        const float* __restrict__ row = logit + (long long)r * 2 * b;
+        const float xr = row[i], xf = row[b + i];
         bad |= ((__float_as_uint(xr) & 0x7f800000u) == 0x7f800000u) | ((__float_as_uint(xf) & 0x7f800000u) == 0x7f800000u);
         const double real = (double)xr, fake = (double)xf;
         sr = sr + real;
@@ -54,12 +62,14 @@ __global__ __launch_bounds__(LECAM_THREADS) void lecam_kernel(const float* __res
             const double pr = dr * dr, pf = df * df;
             rr = rr + pr;
             ff = ff + pf;
-            const double tr = c * dr, tf = c * df;
-            float gr = (float)((double)dld[i] + tr), gf = (float)((double)dld[b + i] + tf);
-            gr = gr != gr ? __uint_as_float(0x7fc00000u) : gr;   // a written NaN is the canonical one
-            gf = gf != gf ? __uint_as_float(0x7fc00000u) : gf;
-            dld[i] = gr;
-            dld[b + i] = gf;
+            if (!ROWS || r == rank) {
+                const double tr = c * dr, tf = c * df;
+                float gr = (float)((double)dld[i] + tr), gf = (float)((double)dld[b + i] + tf);
+                gr = gr != gr ? __uint_as_float(0x7fc00000u) : gr;   // a written NaN is the canonical one
+                gf = gf != gf ? __uint_as_float(0x7fc00000u) : gf;
+                dld[i] = gr;
+                dld[b + i] = gf;
+            }
         }
     }
     s_rr[tid] = rr;
@@ -74,13 +84,13 @@ __global__ __launch_bounds__(LECAM_THREADS) void lecam_kernel(const float* __res
         for (int j = 0; j < LECAM_THREADS; ++j) any_bad |= s_bad[j];
         double r = 0.0;
         if (!warm) {
-            r = (sum_rr + sum_ff) / bb;
+            r = (sum_rr + sum_ff) / nn;
             r = r != r ? __longlong_as_double(0x7ff8000000000000LL) : r;
         }
         state[3] = r;
         loss[0] = (float)r;
         if (!any_bad) {
-            const double m_r = sum_r / bb, m_f = sum_f / bb;
+            const double m_r = sum_r / nn, m_f = sum_f / nn;
             const double g = warm ? 0.0 : decay;
             const double k = 1.0 - g;
             const double gr = g * a_r, kr = k * m_r, gf = g * a_f, kf = k * m_f;
@@ -100,7 +110,19 @@ extern "C" int xmc_lecam(const float* logit, float* dld, int32_t b, double* stat
     XMC_REQUIRE(((uintptr_t)logit % 4) == 0 && ((uintptr_t)dld % 4) == 0 && ((uintptr_t)loss % 4) == 0 && ((uintptr_t)state % 8) == 0);
     XMC_REQUIRE(lam >= 0.0 && lam <= 1.7976931348623157e308 && decay >= 0.0 && decay < 1.0 && start >= 0);
     XMC_REQUIRE(one_sided == 0 || one_sided == 1);
-    hipLaunchKernelGGL(lecam_kernel, dim3(1), dim3(LECAM_THREADS), 0, static_cast<hipStream_t>(stream), logit, dld, (int)b, state,
-                       loss, lam, decay, (int)start, (int)one_sided);
+    hipLaunchKernelGGL((lecam_kernel<false>), dim3(1), dim3(LECAM_THREADS), 0, static_cast<hipStream_t>(stream), logit, 1, 0, dld,
+                       (int)b, state, loss, lam, decay, (int)start, (int)one_sided);
+    XMC_LAUNCH_RET();
+}
+
+extern "C" int xmc_lecam_rows(const float* rows, int32_t w, int32_t rank, float* dld, int32_t b, double* state, float* loss,
+                              double lam, double decay, int32_t start, int32_t one_sided, void* stream) {
+    XMC_REQUIRE(rows && dld && state && loss && w >= 1 && rank >= 0 && rank < w && b >= 1);
+    XMC_REQUIRE((int64_t)w * 2 * (int64_t)b <= 2147483647LL);
+    XMC_REQUIRE(((uintptr_t)rows % 4) == 0 && ((uintptr_t)dld % 4) == 0 && ((uintptr_t)loss % 4) == 0 && ((uintptr_t)state % 8) == 0);
+    XMC_REQUIRE(lam >= 0.0 && lam <= 1.7976931348623157e308 && decay >= 0.0 && decay < 1.0 && start >= 0);
+    XMC_REQUIRE(one_sided == 0 || one_sided == 1);
+    hipLaunchKernelGGL((lecam_kernel<true>), dim3(1), dim3(LECAM_THREADS), 0, static_cast<hipStream_t>(stream), rows, (int)w,
+                       (int)rank, dld, (int)b, state, loss, lam, decay, (int)start, (int)one_sided);
     XMC_LAUNCH_RET();
 }

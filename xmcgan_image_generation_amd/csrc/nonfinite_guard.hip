@@ -1,6 +1,8 @@
 // config.skip_nonfinite_updates: the verdict of a half step -- does anything it is about to commit (gradient arenas, the new
 // u0, the new BatchNorm running statistics) hold a NaN or an infinity? -- and the conditional copy that commits the small
 // state buffers.  The guarded optimiser and accumulator launches read verdict[0] (pointwise.hip, spectral_batched.hip).
+// With data-parallel replicas each rank's scan writes a LOCAL verdict, the locals are all-gathered, and
+// xmc_verdict_merge turns the same rows into the same verdict and the same counters on every rank.
 // Plain kernel launches on the caller's stream: a captured training step replays them, and the host never reads the verdict.
 #include "common.h"
 
@@ -31,6 +33,19 @@ struct nfg_partial {
 
 // exponent bits all ones: NaN, +inf, -inf
 __device__ __forceinline__ int bad_bits(uint32_t x) { return (x & 0x7f800000u) == 0x7f800000u; }
+
+// the persistent counters behind a verdict: [0] skipped in total, [1] the current run, [2] the longest run (all saturating)
+__device__ __forceinline__ void advance_counters(bool bad, int* __restrict__ counters) {
+    if (bad) {
+        const int total = counters[0], run = counters[1];
+        counters[0] = total < 2147483647 ? total + 1 : total;
+        const int r = run < 2147483647 ? run + 1 : run;
+        counters[1] = r;
+        if (r > counters[2]) counters[2] = r;
+    } else {
+        counters[1] = 0;
+    }
+}
 
 __global__ __launch_bounds__(NFG_THREADS) void nonfinite_scan_kernel(nfg_table t, int nseg, nfg_partial* __restrict__ ws) {
     __shared__ long long s_bad[NFG_THREADS / 64];
@@ -120,15 +135,45 @@ __global__ __launch_bounds__(NFG_THREADS) void nonfinite_finish_kernel(const nfg
         verdict[1] = bad > 2147483647LL ? 2147483647 : (int)bad;
         verdict[2] = bad > 0 ? first : -1;
         verdict[3] = 0;
-        if (bad > 0) {                                   // [0] skipped in total, [1] the current run, [2] the longest run
-            const int total = counters[0], run = counters[1];
-            counters[0] = total < 2147483647 ? total + 1 : total;
-            const int r = run < 2147483647 ? run + 1 : run;
-            counters[1] = r;
-            if (r > counters[2]) counters[2] = r;
-        } else {
-            counters[1] = 0;
-        }
+        advance_counters(bad > 0, counters);
+    }
+}
+
+// ---------------------------------------------------------------------------------------------- xmc_verdict_merge
+// One workgroup over the all-gathered local verdicts rows[w][4] of the replicas: every rank reads the same rows
+// and writes the same verdict and the same counters.  Integer adds and a minimum: any order gives the same bits.  No atomics.
+__global__ __launch_bounds__(NFG_THREADS) void verdict_merge_kernel(const int* __restrict__ rows, int w, int* __restrict__ verdict,
+                                                                    int* __restrict__ counters) {
+    __shared__ long long s_bad[NFG_THREADS / 64];
+    __shared__ int s_first[NFG_THREADS / 64];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    long long bad = 0;                                   // sum of the ranks' counts: w < 2^29 values below 2^31
+    int first = NFG_NONE;                                // the lowest rank with a bad verdict
+    for (int r = tid; r < w; r += NFG_THREADS) {
+        bad += rows[4 * (long long)r + 1];
+        if (rows[4 * (long long)r] != 0 && r < first) first = r;
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        bad += __shfl_down(bad, o, 64);
+        const int f = __shfl_down(first, o, 64);
+        first = f < first ? f : first;
+    }
+    if (lane == 0) {
+        s_bad[wave] = bad;
+        s_first[wave] = first;
+    }
+    __syncthreads();
+    if (tid == 0) {
+        bad = s_bad[0] + s_bad[1] + s_bad[2] + s_bad[3];
+        first = s_first[0];
+        for (int k = 1; k < NFG_THREADS / 64; ++k) first = s_first[k] < first ? s_first[k] : first;
+        const bool any = first != NFG_NONE;
+        verdict[0] = any ? 1 : 0;
+        verdict[1] = bad > 2147483647LL ? 2147483647 : (int)bad;
+        verdict[2] = any ? rows[4 * (long long)first + 2] : -1;
+        verdict[3] = any ? first : 0;
+        advance_counters(any, counters);
     }
 }
 
@@ -186,6 +231,14 @@ extern "C" int xmc_nonfinite_verdict(const float* const* ptrs, const int64_t* n_
     hipStream_t s = static_cast<hipStream_t>(stream);
     hipLaunchKernelGGL(nonfinite_scan_kernel, dim3(grid), dim3(NFG_THREADS), 0, s, t, (int)nseg, static_cast<nfg_partial*>(ws));
     hipLaunchKernelGGL(nonfinite_finish_kernel, dim3(1), dim3(NFG_THREADS), 0, s, static_cast<const nfg_partial*>(ws), grid, verdict,
+                       counters);
+    XMC_LAUNCH_RET();
+}
+
+extern "C" int xmc_verdict_merge(const int32_t* rows, int32_t w, int32_t* verdict, int32_t* counters, void* stream) {
+    XMC_REQUIRE(rows && verdict && counters && w >= 1 && 4 * (int64_t)w <= 2147483647LL);
+    XMC_REQUIRE(((uintptr_t)rows % 4) == 0 && ((uintptr_t)verdict % 4) == 0 && ((uintptr_t)counters % 4) == 0);
+    hipLaunchKernelGGL(verdict_merge_kernel, dim3(1), dim3(NFG_THREADS), 0, static_cast<hipStream_t>(stream), rows, (int)w, verdict,
                        counters);
     XMC_LAUNCH_RET();
 }

@@ -100,6 +100,7 @@ class GradSync:
         self.schedule = schedule
         self.group = group
         self.world = dist.get_world_size(group)
+        self.rank = dist.get_rank(group)
         self.bucket = int(bucket_elems)
         self.transport = transport
         self._works = {}
@@ -160,6 +161,36 @@ class GradSync:
             if half.is_cuda:
                 half.record_stream(torch.cuda.current_stream())  # ... and widened on the consumer's stream
             dst.copy_(half)                                      # widen the summed bf16 gradients back into the arena
+
+    def gather_rows(self, row):
+        """row (n,) float32 or int32 -> (world, n): the rows of all replicas in rank order.  Issued on -- and synchronous with
+        respect to -- the current stream; capturable like ``BNGroups.gather_rows``.  What the controllers that must agree on
+        every rank are decided from (ADA's p, the LeCam anchors, the non-finite guard's verdict): an all-gather
+        followed -- in the caller -- by one fixed-order kernel over all rows, never a sum all-reduce, so that every rank
+        computes the same bits under gloo and RCCL alike.
+
+        Exclusive schedule only (ValueError otherwise), and that is why the GRADIENT communicator may be reused here: under it
+        every exchange has been waited for before the next collective is issued, so nothing is in flight on this group beside
+        the gather, and every rank issues the same collectives in the same (program) order.  Under the overlapped schedule a
+        sliced gradient exchange would be running on the side stream, and the order in which the two reach the communicator
+        would be decided by the streams of each rank: a deadlock hazard."""
+        if not self.exclusive:
+            raise ValueError("GradSync.gather_rows needs GradSync(schedule='exclusive'): under the overlapped schedule gradient "
+                             "slices are in flight on this communicator beside the caller's stream")
+        if row.dtype not in (torch.float32, torch.int32):
+            raise ValueError(f"GradSync.gather_rows takes float32 or int32 rows, got {row.dtype}")
+        row = row.contiguous().view(-1)
+        out = torch.empty((self.world, row.numel()), dtype=row.dtype, device=row.device)
+        dist.all_gather_into_tensor(out.view(-1), row, group=self.group)      # (the concatenated form: gloo takes no other)
+        return out
+
+    def logit_rows(self, logit, b, rows=None):
+        """-> the all-gathered (world, 2b) float32 rows, in rank order, of the discriminator's (2b,) logit vector ``logit``.
+        ``rows``: the rows when another controller of the same half step has gathered them already -- one gather serves ADA
+        and LeCam."""
+        if rows is None:
+            rows = self.gather_rows(logit.detach().float().reshape(-1)[:2 * int(b)])
+        return rows
 
     def mean_metrics(self, metrics: dict) -> dict:
         """TrainMetrics.gather_from_model_output (xmc_gan.py:185-190): mean over replicas."""

@@ -11,7 +11,8 @@ adjustment) / (``ada_kimg`` * 1000), clamped to [0, ``P_MAX``].
 This module is NumPy first: ``gate`` and ``update`` are the written specification of ``xmc_ada_gate`` / ``xmc_ada_update``
 (csrc/ada.hip).  Both are exact -- a select on a float64 comparison, integer counts, and five IEEE double operations in a fixed
 order -- so the kernels are held to them bit for bit.  ``AdaController`` owns the persistent state in device memory and runs the
-kernels where the operator table has them, the specification otherwise.
+kernels where the operator table has them, the specification otherwise.  With data-parallel replicas the signs
+are counted over the all-gathered logits of every rank: ``update_rows`` is the specification of ``xmc_ada_update_rows``.
 """
 from __future__ import annotations
 
@@ -113,6 +114,17 @@ def update(state, real_logits, target, images_to_full, interval, p_max) -> np.nd
     return s
 
 
+def update_rows(state, rows, b, target, images_to_full, interval, p_max) -> np.ndarray:
+    """The specification of ``xmc_ada_update_rows``: the controller with data-parallel replicas.  ``rows``: float32 (w, 2b), the
+    logit vectors [real; fake] of all w ranks in rank order.  Exactly ``update`` on the concatenation of the real halves
+    ``rows[r, :b]`` in rank order -- the counts are integers, so every rank computes the same bits from the same rows.
+    ``images_to_full`` counts GLOBAL images, as the paper's ``ada_kimg`` means."""
+    rows, b = np.asarray(rows, np.float32), int(b)
+    if rows.ndim != 2 or b < 1 or rows.shape[0] < 1 or rows.shape[1] != 2 * b:
+        raise ValueError(f"ada.update_rows: rows must be (w, 2b) with w, b >= 1, got {rows.shape}, b = {b}")
+    return update(state, rows[:, :b].reshape(-1), target, images_to_full, interval, p_max)
+
+
 class AdaController:
     """The controller's persistent ``float64[8]`` state in device memory (outside the step's pool, so a captured step replays
     on it) and the two launches that use it.  On ``HipOps`` ``gate`` is ``xmc_ada_gate`` and ``update`` is ``xmc_ada_update``:
@@ -138,12 +150,23 @@ class AdaController:
         rows = torch.where(on, aug, ident)
         return rows.transpose(0, 1).reshape(2 * aug.shape[0], diff_augment.PLAN_WIDTH).contiguous()
 
-    def update(self, ops, logit, b):
-        """one half step: ``logit`` is D's (2B,) float32 logit vector, whose first ``b`` entries are the real half"""
+    def update(self, ops, logit, b, replicas=None, rows=None):
+        """one half step: ``logit`` is D's (2B,) float32 logit vector, whose first ``b`` entries are the real half.  ``replicas``
+        (the step's ``dp.GradSync``, exclusive schedule): the signs are counted over the real halves of ALL ranks' logits
+        (``GradSync.logit_rows``; ``rows``: already gathered), so every rank holds the same p"""
         import torch
         if self.settings is None:
             raise ValueError("AdaController.update needs the controller's settings (built without a config)")
         s = self.settings
+        if replicas is not None:
+            rows = replicas.logit_rows(logit, b, rows)
+            if hasattr(ops, "ada_update_rows"):
+                ops.ada_update_rows(rows, b, self.state, s["target"], s["images_to_full"], s["interval"], self.p_max)
+                return
+            new = update_rows(self.state.cpu().numpy(), rows.float().cpu().numpy(), b, s["target"], s["images_to_full"],
+                              s["interval"], self.p_max)
+            self.state.copy_(torch.from_numpy(new))
+            return
         if hasattr(ops, "ada_update"):
             ops.ada_update(logit, b, self.state, s["target"], s["images_to_full"], s["interval"], self.p_max)
             return

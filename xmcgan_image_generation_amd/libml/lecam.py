@@ -8,7 +8,9 @@ effect on the backward pass is ``dld += 2 * lambda / b * (logit - anchor)`` on t
 
 This module is NumPy first: ``step`` is the written specification of ``xmc_lecam`` (csrc/lecam.hip).  It is IEEE double arithmetic
 in a fixed order -- the sums included (``fixed_sum``) -- so the kernel is held to it bit for bit.  ``LecamController`` owns the
-persistent state in device memory and runs the kernel where the operator table has it, the specification otherwise.
+persistent state in device memory and runs the kernel where the operator table has it, the specification otherwise.  With
+data-parallel replicas R and the anchors come from the all-gathered logits of every rank: ``step_rows`` is the
+specification of ``xmc_lecam_rows``.
 
 ``lecam_decay`` = 0.99 is the paper's decay as far as it can be recalled here, and 0.3 (CIFAR scale) / 0.01 (ImageNet scale) are its
 weights: policy defaults, NOT tuned in this project.
@@ -121,6 +123,55 @@ def step(state, logit, b, dld, lam, decay, start, one_sided=False):
         return s, g32, np.float32(r)
 
 
+def step_rows(state, rows, rank, dld, lam, decay, start, one_sided=False):
+    """The specification of ``xmc_lecam_rows``: one half step with data-parallel replicas.  ``rows``: float32 (w, 2b), the logit
+    vectors [real; fake] of all w ranks in rank order; ``dld``: THIS rank's float32 (2b,) hinge gradient; ``rank``: its row.
+    -> (new state, new dld, float32 R).  Steps 1 - 4 of ``step`` with X_R / X_F = the ranks' real / generated halves concatenated
+    in rank order (w b elements each): R and the two means divide by w b, and "all finite" covers all w * 2b logits, so the state
+    and R are the same bits on every rank.  Only this rank's gradient takes the term: c = (2 lam) / b with the LOCAL b and the
+    d_i of row ``rank`` -- the optimiser's 1 / w gradient scale makes the ranks' sum the gradient of lam * R."""
+    s = np.array(state, np.float64).reshape(STATE_WIDTH).copy()
+    x32 = np.asarray(rows, np.float32)
+    g32 = np.asarray(dld, np.float32).reshape(-1).copy()
+    if x32.ndim != 2 or x32.shape[0] < 1 or x32.shape[1] < 2 or x32.shape[1] % 2:
+        raise ValueError(f"lecam.step_rows: rows must be (w, 2b) with w, b >= 1, got {x32.shape}")
+    w, b = x32.shape[0], x32.shape[1] // 2
+    rank = int(rank)
+    if not 0 <= rank < w or g32.shape != (2 * b,):
+        raise ValueError(f"lecam.step_rows: rank must be in [0, {w}) and dld ({2 * b},), got {rank}, {g32.shape}")
+    x = x32.astype(np.float64)
+    real, fake = x[:, :b].reshape(-1), x[:, b:].reshape(-1)
+    own = slice(rank * b, (rank + 1) * b)
+    a_r, a_f, ticks, updates = s[ANCHOR_REAL], s[ANCHOR_FAKE], s[TICKS], s[UPDATES]
+    bb, nn = np.float64(b), np.float64(w * b)
+    with np.errstate(all="ignore"):
+        # 1. active test
+        active = ticks >= np.float64(int(start)) and updates > 0.0
+        # 2. penalty
+        r = np.float64(0.0)
+        if active:
+            dr, df = real - a_f, fake - a_r
+            if one_sided:
+                dr, df = np.where(dr > 0.0, dr, 0.0), np.where(df < 0.0, df, 0.0)
+            r = (fixed_sum(dr * dr) + fixed_sum(df * df)) / nn
+            c = (np.float64(2.0) * np.float64(lam)) / bb
+            new = (g32.astype(np.float64) + c * np.concatenate([dr[own], df[own]])).astype(np.float32)
+            g32 = np.where(np.isnan(new), _QNAN32, new)
+            r = _QNAN64 if np.isnan(r) else r
+        s[LAST_R] = r
+        # 3. anchor update, from the anchors read above
+        if bool(np.isfinite(x32).all()):
+            m_r, m_f = fixed_sum(real) / nn, fixed_sum(fake) / nn
+            g = np.float64(0.0) if (ticks < np.float64(int(start)) or updates == 0.0) else np.float64(decay)
+            k = np.float64(1.0) - g
+            s[ANCHOR_REAL] = g * a_r + k * m_r
+            s[ANCHOR_FAKE] = g * a_f + k * m_f
+            s[UPDATES] = updates + 1.0
+        # 4. tick
+        s[TICKS] = ticks + 1.0
+        return s, g32, np.float32(r)
+
+
 class LecamController:
     """The regulariser's persistent ``float64[8]`` state in device memory (outside the step's pool, so a captured step replays on
     it) and the one launch that uses it.  On ``HipOps`` ``apply`` is ``xmc_lecam``: no host read, one graph launch per step stays
@@ -133,13 +184,24 @@ class LecamController:
         self.settings = settings(config) if config is not None else None
 
     # ------------------------------------------------------------------------------------------------ device side
-    def apply(self, ops, logit, dld, b):
+    def apply(self, ops, logit, dld, b, replicas=None, rows=None):
         """one half step: ``logit`` is D's (2B,) float32 logit vector [real; fake], ``dld`` the (2B,) float32 gradient the hinge
-        launch has just written, which takes the term IN PLACE.  -> (1,) float32: the unweighted R"""
+        launch has just written, which takes the term IN PLACE.  -> (1,) float32: the unweighted R.  ``replicas`` (the step's
+        ``dp.GradSync``, exclusive schedule): R and the anchors come from ALL ranks' logits (``GradSync.logit_rows``; ``rows``:
+        already gathered), so every rank holds the same anchors and reports the same R"""
         import torch
         if self.settings is None:
             raise ValueError("LecamController.apply needs the controller's settings (built without a config)")
         s = self.settings
+        if replicas is not None:
+            rows = replicas.logit_rows(logit, b, rows)
+            if hasattr(ops, "lecam_rows"):
+                return ops.lecam_rows(rows, replicas.rank, dld, b, self.state, s["weight"], s["decay"], s["start"], s["one_sided"])
+            new, grad, r = step_rows(self.state.cpu().numpy(), rows.float().cpu().numpy(), replicas.rank,
+                                     dld.detach().float().cpu().numpy(), s["weight"], s["decay"], s["start"], s["one_sided"])
+            self.state.copy_(torch.from_numpy(new))
+            dld.copy_(torch.from_numpy(grad))
+            return torch.from_numpy(np.asarray([r], np.float32)).to(dld.device)
         if hasattr(ops, "lecam"):
             return ops.lecam(logit, dld, b, self.state, s["weight"], s["decay"], s["start"], s["one_sided"])
         new, grad, r = step(self.state.cpu().numpy(), logit.detach().float().cpu().numpy(), b, dld.detach().float().cpu().numpy(),

@@ -1096,6 +1096,41 @@ class HipOps:
                                  self._stream()), "xmc_lecam")
         return loss
 
+    # ------------------------------------------------------------------ the three controllers with replicas
+    def _logit_rows(self, rows, b):
+        w = rows.shape[0]
+        assert rows.dtype == torch.float32 and tuple(rows.shape) == (w, 2 * int(b)) and rows.is_contiguous() and rows.is_cuda
+        return w
+
+    def ada_update_rows(self, rows, b, state, target, images_to_full, interval, p_max):
+        """``ada_update`` over the real halves of the all-gathered logit rows ``rows`` (world, 2B) in rank order
+        (``xmc_ada_update_rows``; specification: ``ada.update_rows``).  One launch of one workgroup, capturable."""
+        w = self._logit_rows(rows, b)
+        assert state.dtype == torch.float64 and state.numel() >= 8 and state.is_contiguous() and state.device == rows.device
+        check(self.lib.xmc_ada_update_rows(_p(rows), w, int(b), _p(state), float(target), float(images_to_full), int(interval),
+                                           float(p_max), self._stream()), "xmc_ada_update_rows")
+
+    def lecam_rows(self, rows, rank, dld, b, state, lam, decay, start, one_sided):
+        """``lecam`` with replicas (``xmc_lecam_rows``; specification: ``lecam.step_rows``): R and the anchors come from the
+        all-gathered logit rows ``rows`` (world, 2B) of every rank, ``dld`` (2B,) -- this rank's gradient -- takes the term of
+        row ``rank`` in place.  -> (1,) float32: the unweighted global R.  One launch of one workgroup, capturable."""
+        b = int(b)
+        w = self._logit_rows(rows, b)
+        assert dld.dtype == torch.float32 and dld.dim() == 1 and dld.numel() == 2 * b and dld.device == rows.device
+        assert state.dtype == torch.float64 and state.numel() >= 8 and state.is_contiguous() and state.device == rows.device
+        loss = self.zeros((1,))
+        check(self.lib.xmc_lecam_rows(_p(rows), w, int(rank), _p(dld), b, _p(state), _p(loss), float(lam), float(decay), int(start),
+                                      int(bool(one_sided)), self._stream()), "xmc_lecam_rows")
+        return loss
+
+    def verdict_merge(self, rows, verdict, counters):
+        """verdict (int32[4]) and the persistent ``counters`` (int32[4]) from the all-gathered local verdicts ``rows`` (world, 4)
+        (``xmc_verdict_merge``; specification: ``nonfinite_guard.merge_rows``).  One launch of one workgroup, capturable."""
+        assert rows.dtype == torch.int32 and rows.dim() == 2 and rows.shape[1] == 4 and rows.is_contiguous() and rows.is_cuda
+        assert verdict.dtype == torch.int32 and verdict.numel() >= 4 and verdict.is_contiguous() and verdict.device == rows.device
+        assert counters.dtype == torch.int32 and counters.numel() >= 4 and counters.is_contiguous() and counters.device == rows.device
+        check(self.lib.xmc_verdict_merge(_p(rows), rows.shape[0], _p(verdict), _p(counters), self._stream()), "xmc_verdict_merge")
+
     # ------------------------------------------------------------------ pairwise sample metrics (utils/sample_metrics.py)
     def sample_pool(self, x):
         """an (n, d) float32 pool on this table's device (a NumPy array is uploaded; a device tensor is taken as it is), so that a

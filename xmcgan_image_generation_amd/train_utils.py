@@ -151,10 +151,7 @@ def train_step(rng, state, batch, gan_model=xmc_gan, generator=None, discriminat
     ``d_aug_host`` (config.diff_augment): the host copy of ``batch["d_aug"]`` when that is a device tensor the caller cannot have
     read back here (``GraphedTrainStep``'s capture); otherwise it is made from the batch."""
     n = config.d_step_per_g_step
-    if grad_sync is not None and config.get("skip_nonfinite_updates", False):
-        raise ValueError("config.skip_nonfinite_updates is not supported with replicas (grad_sync): the verdict of a half step must "
-                         "exist before any of its updates is applied, which the deferred and bucketed discriminator update of the "
-                         "data-parallel schedule does not allow")
+    xmc_gan.check_guard_replicas(config, grad_sync)
     if gan_model is xmc_gan:
         xmc_gan.check_ada_replicas(config, grad_sync)
         xmc_gan.check_lecam_replicas(config, grad_sync)
@@ -571,6 +568,26 @@ def _array_fields(batch):
     return {k: torch.as_tensor(v) for k, v in batch.items() if isinstance(v, (torch.Tensor, np.ndarray))}
 
 
+def check_replica_drift(states, grad_sync):
+    """The tripwire of DESIGN.md 9f.3: ``states`` maps a controller's name to its small device state (float64[8] / int32[4]; None =
+    the switch is off), which every replica must hold BIT FOR BIT -- rank 0's checkpoint is then everybody's.  The states are
+    all-gathered and compared on the host (``train`` reads them at a checkpoint boundary anyway); RuntimeError names the
+    controller and the first rank that differs from rank 0."""
+    import torch.distributed as dist
+    for name, t in sorted(states.items()):
+        if t is None:
+            continue
+        bits = t.detach().contiguous().view(torch.int32).reshape(-1)
+        out = torch.empty((grad_sync.world, bits.numel()), dtype=torch.int32, device=bits.device)
+        dist.all_gather_into_tensor(out.view(-1), bits, group=grad_sync.group)
+        out = out.cpu()
+        for r in range(1, grad_sync.world):
+            if not torch.equal(out[r], out[0]):
+                raise RuntimeError(f"train: the {name} controller's state on rank {r} differs from rank 0's: the replicas have "
+                                   f"drifted apart, and a checkpoint would hold rank 0's state alone (as int32 words: rank 0 "
+                                   f"{out[0].tolist()}, rank {r} {out[r].tolist()})")
+
+
 def train(config, workdir, test_mode=False, *, datasets=None):
     """The training loop (reference train_utils.py:312-461).  Resumes from the newest checkpoint of ``workdir/checkpoints-0``;
     every ``eval_every_steps`` (and on the last step) the averaged train metrics go to ``workdir/metrics.jsonl`` and three sample
@@ -609,7 +626,11 @@ def train(config, workdir, test_mode=False, *, datasets=None):
         bn_groups = generator(train=True).bn_groups
         # cross-replica BatchNorm groups issue collectives from inside the generator's passes: only the exclusive schedule
         # keeps the gradient exchange out of their way (dp.check_schedule)
-        grad_sync = GradSync(schedule="exclusive", bn_groups=bn_groups) if bn_groups is not None else GradSync()
+        # ... and config.ada_target, config.lecam_weight and config.skip_nonfinite_updates are decided from rows that the replicas
+        # all-gather on the gradient communicator (GradSync.gather_rows): the exclusive schedule too
+        from .libml import ada as _ada, lecam as _lecam, nonfinite_guard as _guard
+        shared = _ada.enabled(config) or _lecam.enabled(config) or _guard.enabled(config)
+        grad_sync = GradSync(schedule="exclusive", bn_groups=bn_groups) if (bn_groups is not None or shared) else GradSync()
     if writes and initial_step == 1:                 # the reference's writer.write_hparams (:402-403)
         import json
         with open(os.path.join(workdir, "config.json"), "w") as f:
@@ -714,6 +735,9 @@ def train(config, workdir, test_mode=False, *, datasets=None):
                 visualize = split_input_dict(batch, n_split)[0]
                 grids = generate_batch(fold_in(streams["sample_batch"], step), state, visualize, generator, config)
                 write_image_grids(os.path.join(workdir, "images"), step, grids)
+        if write_checkpoint and grad_sync is not None:
+            check_replica_drift({"ada": ada.state if ada is not None else None, "lecam": lecam.state if lecam is not None else None,
+                                 "guard": guard.counters if guard is not None else None}, grad_sync)
         if write_checkpoint and writes:
             if guard is not None:                    # Adam's t on the host = the number of APPLIED updates (the device's counter)
                 state.g_optimizer.arena.sync_opt_step()

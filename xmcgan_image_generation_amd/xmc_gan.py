@@ -305,11 +305,18 @@ def _ada_of(state, config):
     return state.ada
 
 
+def _shares_rows(grad_sync):
+    """can the replicas of this exchange decide a controller together?  Only under ``dp.GradSync(schedule='exclusive')``, whose
+    ``gather_rows`` the three controllers below share"""
+    return getattr(grad_sync, "exclusive", False) is True
+
+
 def check_ada_replicas(config, grad_sync):
-    """config.ada_target with replicas is an error, the same decision as for config.skip_nonfinite_updates"""
-    if grad_sync is not None and ada_lib.enabled(config):
-        raise ValueError("config.ada_target is not supported with replicas (grad_sync): every replica would run a controller of "
-                         "its own on its own logits, their p would drift apart, and only rank 0's would be checkpointed")
+    """config.ada_target with replicas needs the exclusive gradient schedule: one p, decided from every replica's logits"""
+    if grad_sync is not None and ada_lib.enabled(config) and not _shares_rows(grad_sync):
+        raise ValueError("config.ada_target with replicas (grad_sync) needs GradSync(schedule='exclusive'): otherwise every replica "
+                         "would run a controller of its own on its own logits, their p would drift apart, and only rank 0's would "
+                         "be checkpointed")
 
 
 def _lecam_of(state, config):
@@ -323,10 +330,19 @@ def _lecam_of(state, config):
 
 
 def check_lecam_replicas(config, grad_sync):
-    """config.lecam_weight with replicas is an error, the same decision as for config.ada_target"""
-    if grad_sync is not None and lecam_lib.enabled(config):
-        raise ValueError("config.lecam_weight is not supported with replicas (grad_sync): every replica would keep anchors of its "
-                         "own from its own logits, they would drift apart, and only rank 0's would be checkpointed")
+    """config.lecam_weight with replicas needs the exclusive gradient schedule, the same decision as for config.ada_target"""
+    if grad_sync is not None and lecam_lib.enabled(config) and not _shares_rows(grad_sync):
+        raise ValueError("config.lecam_weight with replicas (grad_sync) needs GradSync(schedule='exclusive'): otherwise every replica "
+                         "would keep anchors of its own from its own logits, they would drift apart, and only rank 0's would be "
+                         "checkpointed")
+
+
+def check_guard_replicas(config, grad_sync):
+    """config.skip_nonfinite_updates with replicas needs the exclusive gradient schedule: one verdict for every replica"""
+    if grad_sync is not None and nonfinite_guard.enabled(config) and not _shares_rows(grad_sync):
+        raise ValueError("config.skip_nonfinite_updates with replicas (grad_sync) needs GradSync(schedule='exclusive'): the deferred "
+                         "and bucketed discriminator update of the overlapped schedule applies gradients before a verdict over the "
+                         "whole half step can exist")
 
 
 def _augment_pullback(ops, d_tape, dimg):
@@ -358,8 +374,10 @@ def _generator_forward(rng, config, state, batch, g, need_tape):
 
 
 def _forward(rng, config, state, batch, g, d, need_g_tape, image_model=None, after_trunk=None, want_metrics=True, stats=None,
-             clip=None):
-    """``stats`` (a ``TrainStatistics``, train_g_d only): the discriminator forward also computes the heads' accuracy / entropy
+             clip=None, replicas=None):
+    """``replicas`` (the step's exclusive ``dp.GradSync``, or None): config.ada_target and config.lecam_weight are decided from the
+    logits of every replica -- ONE all-gather of the logit vector, behind the discriminator's forward pass, serves both.
+    ``stats`` (a ``TrainStatistics``, train_g_d only): the discriminator forward also computes the heads' accuracy / entropy
     pairs and hands its logits, losses and sigmas to it.  ``clip`` (a ``ClipGuidance``, train_g_d with config.clip_guidance_weight
     only): the frozen CLIP image tower's forward on the generated images, with its tape"""
     ops = g.ops
@@ -428,22 +446,26 @@ def _forward(rng, config, state, batch, g, d, need_g_tape, image_model=None, aft
                                                 **({"want_stats": True} if stats is not None else {}))
     if stats is not None:
         stats.note_forward(logit, loss_vec, d.last_stats, d._sn_ctx[3])
-    if aug_ctx is not None and _ada_of(state, config) is not None:
+    b = img.shape[0]
+    ada_on, lecam_on = aug_ctx is not None and _ada_of(state, config) is not None, _lecam_of(state, config) is not None
+    rows_kw = {}
+    if replicas is not None and (ada_on or lecam_on):
+        rows_kw = dict(replicas=replicas, rows=replicas.logit_rows(logit, b))
+    if ada_on:
         # config.ada_target: the controller reads the real half of the logits on the stream the discriminator's forward ran on
         # -- the next half step's gate reads the new p in stream order.  Forward values only: not under the non-finite guard's
         # verdict (non-finite logits are not counted)
-        state.ada.update(ops, logit, img.shape[0])
+        state.ada.update(ops, logit, b, **rows_kw)
     if aug_ctx is not None:
         d_tape["d_aug"] = aug_ctx            # train_g_d pulls the generated half's gradient back through it
-    b = img.shape[0]
     hinge = ops.zeros((2,))
     dld, dlg = losses.hinge_loss(ops, logit, b, hinge[0:1], hinge[1:2])      # xmc_gan.py:144-145
     lecam_r = None
-    if _lecam_of(state, config) is not None:
+    if lecam_on:
         # config.lecam_weight (not in the reference): dld takes 2 lambda / b * (logit - anchor) in place, directly behind the hinge
         # launch on its stream, and the anchors move.  dlg, the hinge slots and d_loss stay as they are.  Forward values only: not
         # under the non-finite guard's verdict (a batch with a non-finite logit leaves the anchors alone)
-        lecam_r = state.lecam.apply(ops, logit, dld, b)
+        lecam_r = state.lecam.apply(ops, logit, dld, b, **rows_kw)
     if not want_metrics:                     # train_d discards them (xmc_gan.py:238-256 returns the state only)
         out = None
     elif hasattr(ops, "loss_assemble"):      # one launch instead of ten scalar adds in front of the backward pass
@@ -463,9 +485,7 @@ def _guarded(state, config, ops, g, d, grad_sync):
     half step commits into those flat buffers (``xmc_commit_if``) instead of returning new trees.  (state, None) with the switch off."""
     if not nonfinite_guard.enabled(config):
         return state, None
-    if grad_sync is not None:
-        raise ValueError("config.skip_nonfinite_updates is not supported with replicas (grad_sync): the deferred and bucketed "
-                         "discriminator update applies gradients before a verdict over the whole half step can exist")
+    check_guard_replicas(config, grad_sync)
     new = {}
     if getattr(state, "guard", None) is None:
         new["guard"] = nonfinite_guard.NonfiniteGuard(ops.device)
@@ -491,16 +511,18 @@ def _sn_padding(d, u_new):
     return pad
 
 
-def _judge(ops, guard, d, segments, u_new):
+def _judge(ops, guard, d, segments, u_new, replicas=None):
     """the half step's verdict, on the stream where all its gradient producers have joined, in front of the first optimiser launch:
     one scan of everything it is about to commit (``segments``: the gradient arena(s), the new u0 ``u_new``, in train_g_d the new
-    BatchNorm running statistics).  -> verdict (int32[4], device)"""
+    BatchNorm running statistics).  -> verdict (int32[4], device).  ``replicas`` (the step's exclusive ``dp.GradSync``): called
+    behind ``grad_sync.wait``, so the arenas scanned are the exchanged ones -- the same on every rank, and a NaN on one rank is a
+    NaN in the sum; the merge of the ranks' verdicts covers what stays rank-local (G's new running statistics)"""
     pad = _sn_padding(d, u_new)
     if pad.numel():
         u_new.index_fill_(0, pad, 0.0)       # (uninitialised bytes between the slices must not read as a NaN)
     if hasattr(ops, "join_wgrad"):
         ops.join_wgrad()
-    return guard.judge(ops, segments)
+    return guard.judge(ops, segments, replicas=replicas)
 
 
 def _apply_adam(ops, opt, config, lr, grad_scale, ema=None, fix_args=None, net=None, stats=None, verdict=None, fresh_u=None):
@@ -632,7 +654,8 @@ def train_d(rng, state, batch, generator, discriminator, config, grad_sync=None,
         prefetch()
         early = False
     state, out, dld, _, _, d_tape, _new_g_stats, new_sn, _, _ = _forward(rng, config, state, batch, g, d, need_g_tape=False,
-                                                                         after_trunk=prefetch if early else None, want_metrics=False)
+                                                                         after_trunk=prefetch if early else None, want_metrics=False,
+                                                                         replicas=grad_sync)
     keep_async = getattr(ops, "wgrad_async", False)
     if (_ASYNC_WGRAD_D or grad_sync is not None) and hasattr(ops, "wgrad_async"):
         ops.wgrad_async = True
@@ -663,7 +686,7 @@ def train_d(rng, state, batch, generator, discriminator, config, grad_sync=None,
         u0 = state.discriminator_state["spectral_norm_stats"].flat
         # (G's new running statistics are discarded as always, but they are scanned: a NaN the generator's forward pass met
         # shows in its batch statistics even where a max(x, 0) further on turned it into a finite, meaningless image)
-        verdict = _judge(ops, guard, d, [d_arena.grads, new_sn.flat, _new_g_stats.flat], new_sn.flat)
+        verdict = _judge(ops, guard, d, [d_arena.grads, new_sn.flat, _new_g_stats.flat], new_sn.flat, replicas=grad_sync)
         _apply_adam(ops, state.d_optimizer, config, config.d_lr, scale, fix_args=fix_args, net=d, verdict=verdict, fresh_u=u0)
         guard.commit(ops, u0, new_sn.flat)
         return state.replace(prefetched_g=prefetched)
@@ -691,7 +714,8 @@ def train_g_d(rng, state, batch, generator, discriminator, config, additional_da
         stats.bind(ops, d_arena, g_arena)
     clip = additional_data["clip_guidance"] if clip_guidance_weight(config) > 0.0 else None
     state, out, dld, dlg, g_tape, d_tape, new_g_stats, new_sn, pre, cpre = _forward(rng, config, state, batch, g, d, need_g_tape=True,
-                                                                                    image_model=image_model, stats=stats, clip=clip)
+                                                                                    image_model=image_model, stats=stats, clip=clip,
+                                                                                    replicas=grad_sync)
     b = g_tape["b"]
     d_scale = g_scale = 1.0
     c_pre = c_clip = None
@@ -828,7 +852,7 @@ def _finish_g_d(ops, state, config, out, c_pre, new_g_stats, new_sn, d_scale, g_
     if guard is not None:
         bs, u0 = state.generator_state["batch_stats"].flat, state.discriminator_state["spectral_norm_stats"].flat
         verdict = _judge(ops, guard, nets[1], [state.d_optimizer.arena.grads, state.g_optimizer.arena.grads, new_sn.flat,
-                                               new_g_stats.flat], new_sn.flat)
+                                               new_g_stats.flat], new_sn.flat, replicas=grad_sync)
         kw_d, kw_g = dict(verdict=verdict, fresh_u=u0), dict(verdict=verdict)
     if not d_updated:
         _apply_adam(ops, state.d_optimizer, config, config.d_lr, d_scale, fix_args=fix_args, net=nets[1],
