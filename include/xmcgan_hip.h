@@ -1139,6 +1139,58 @@ int xmc_lecam_rows(const float* rows, int32_t w, int32_t rank, float* dld, int32
                    double decay, int32_t start, int32_t one_sided, void* stream);
 int xmc_verdict_merge(const int32_t* rows, int32_t w, int32_t* verdict, int32_t* counters, void* stream);
 
+/* ---- learning-rate and EMA-decay schedules evaluated on the device (config.lr_schedule, config.ema_ramp, ...;
+ *      libml/opt_schedule.py is the specification; csrc/pointwise.hip, csrc/spectral_batched.hip) ----
+ * XMC_ABI_VERSION stays 36: this section only ADDS entry points and a structure, as the sections above did.
+ * `step_state` is float32[8] here: [0] t (int32 bits)  [1] 1 / (1 - beta1^t)  [2] 1 / (1 - beta2^t)  [3] not touched
+ *     [4] lr_t   [5] d_t (the EMA decay of this update)   [6] float32(w f), the rate's factor   [7] not touched
+ * The entry points above read and write slots 0 .. 2 only; they never touch 4 .. 7.
+ * For the update that makes the counter t (t >= 1), in IEEE double, in this order, no multiply fused with an add:
+ *     w = t / warmup if warmup > 0 and t < warmup, else 1
+ *     x = 0 if t <= decay_start;  1 if t >= decay_end;  otherwise (t - decay_start) / (decay_end - decay_start)
+ *     f = 1 (CONSTANT);  1 + (final_ratio - 1) x (LINEAR);  final_ratio + (1 - final_ratio) (0.5 (1 + cos(pi x))) (COSINE)
+ *     lr_t = float32((base w) f);   slot 6 = float32(w f)
+ *     d_t = 0 if t <= ema_start;  else float32(min(ema_decay, (1 + t) / (ema_ramp + t))) if ema_ramp > 0;  else float32(ema_decay)
+ * A CONSTANT schedule without warm-up yields exactly the float32 the host arguments `lr` / `ema_decay` of the parents yield.
+ *  - xmc_adam_ema_dev_sched / xmc_adam_ema_dev_sn_sched: the entry point of the same name without its `lr` and `ema_decay`; ONE
+ *    thread advances t and the two corrections exactly as the parent does and writes slots 4 .. 6 from `sched` (read on the host
+ *    at launch: it travels in the kernel arguments); the Adam kernel behind it is the parent's, with lr and d taken from slots 4
+ *    and 5 -- the same arithmetic on the same values, bit for bit.  `verdict` may be NULL (the unguarded form); otherwise it is
+ *    the int32[4] of xmc_nonfinite_verdict, and verdict[0] != 0 leaves p, m, v, ema and ALL of step_state as they are and zeroes the
+ *    gradient where the parent's guarded form would.
+ *  - xmc_adam_wprep_tiles_sched: xmc_adam_wprep_tiles(_guarded) without `lr` and `ema_decay`, on a step_state that
+ *    xmc_adam_ema_dev_sn_sched has ALREADY advanced for this update; `verdict` may be NULL.
+ * XMC_EINVAL, nothing launched: whatever the parent refuses; sched NULL; an unknown kind; reserved != 0; base not finite or <= 0; a negative warmup,
+ * decay_start, decay_end or ema_start; decay_end <= decay_start on a decaying kind; final_ratio outside [0, 1] or not finite;
+ * ema_decay outside [0, 1); ema_ramp negative or not finite; a verdict that is not 4-byte aligned. */
+#define XMC_SCHED_CONSTANT 0
+#define XMC_SCHED_LINEAR 1
+#define XMC_SCHED_COSINE 2
+typedef struct xmc_opt_schedule {
+    int32_t kind;                /* XMC_SCHED_* */
+    int32_t reserved;            /* 0 */
+    double base;                 /* the base learning rate */
+    int64_t warmup;              /* W: the horizons count updates of THIS optimiser */
+    int64_t decay_start;         /* T0 */
+    int64_t decay_end;           /* T1 (read by the decaying kinds only) */
+    double final_ratio;          /* r */
+    double ema_decay;
+    double ema_ramp;
+    int64_t ema_start;           /* S */
+} xmc_opt_schedule;
+int xmc_adam_ema_dev_sched(float* p, const float* g, float* m, float* v, float* ema, int64_t n, double beta1, double beta2,
+                           float eps, float* step_state, float grad_scale, const xmc_opt_schedule* sched, const int32_t* verdict,
+                           void* stream);
+int xmc_adam_ema_dev_sn_sched(float* p, float* g, float* m, float* v, float* ema, int64_t n, double beta1, double beta2, float eps,
+                              float* step_state, float grad_scale, int32_t zero_grads, const void* map, const void* table,
+                              int32_t n_entries, const float* kvec, const float* scal, const float* u, const float* vv,
+                              const xmc_opt_schedule* sched, const int32_t* verdict, void* stream);
+int xmc_adam_wprep_tiles_sched(const void* table, int32_t n, int32_t blocks, float* p, float* g, float* m, float* v, float* ema,
+                               double beta1, double beta2, float eps, const float* step_state, float grad_scale,
+                               int32_t zero_grads, const float* kvec, const float* scal, const float* u, const float* vv,
+                               void* wf_buf, void* wd_buf, void* pf_buf, void* pd_buf, float* part, const int32_t* verdict,
+                               void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -72,6 +72,12 @@ class TrainStatsArgs(C.Structure):   # mirrors xmc_train_stats_args
                [("d_grad_scale", C.c_float), ("g_grad_scale", C.c_float)]
 
 
+class OptSchedule(C.Structure):      # mirrors xmc_opt_schedule (libml/opt_schedule.Schedule)
+    _fields_ = [("kind", C.c_int32), ("reserved", C.c_int32), ("base", C.c_double), ("warmup", C.c_int64),
+                ("decay_start", C.c_int64), ("decay_end", C.c_int64), ("final_ratio", C.c_double), ("ema_decay", C.c_double),
+                ("ema_ramp", C.c_double), ("ema_start", C.c_int64)]
+
+
 XMC_LN_BWD_ROWS, XMC_LN_BWD_GATHER, XMC_LN_BWD_VISION = 0, 1, 2
 TRAIN_STATS_N = 25                   # XMC_TRAIN_STATS_N
 NONFINITE_MAX_SEGMENTS = 8           # XMC_NONFINITE_MAX_SEGMENTS
@@ -240,6 +246,11 @@ SIGNATURES = {
     "xmc_ada_update_rows": [_P, _I, _I, _P, C.c_double, C.c_double, _I, C.c_double, _P],
     "xmc_lecam_rows": [_P, _I, _I, _P, _I, _P, _P, C.c_double, C.c_double, _I, _I, _P],
     "xmc_verdict_merge": [_P, _I, _P, _P, _P],
+    "xmc_adam_ema_dev_sched": [_P, _P, _P, _P, _P, _L, C.c_double, C.c_double, _F, _P, _F, C.POINTER(OptSchedule), _P, _P],
+    "xmc_adam_ema_dev_sn_sched": [_P, _P, _P, _P, _P, _L, C.c_double, C.c_double, _F, _P, _F, _I, _P, _P, _I, _P, _P, _P, _P,
+                                  C.POINTER(OptSchedule), _P, _P],
+    "xmc_adam_wprep_tiles_sched": [_P, _I, _I, _P, _P, _P, _P, _P, C.c_double, C.c_double, _F, _P, _F, _I, _P, _P, _P, _P, _P, _P, _P,
+                                   _P, _P, _P, _P],
 }
 
 # diagnostic probes: include/xmc_probe.h, libxmc_probe.so (csrc_probe/) -- outside the product ABI

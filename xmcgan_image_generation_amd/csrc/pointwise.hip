@@ -1,5 +1,7 @@
 // Streaming pointwise / resampling kernels (HBM-bound; 16-byte vectors, grid-stride) and the
 // fused Adam(+EMA) arena update.
+#include <cmath>
+
 #include "adam_update.h"
 #include "common.h"
 
@@ -178,7 +180,10 @@ __global__ __launch_bounds__(256) void add_kernel(const T* __restrict__ a, const
 // stays so in BITS: the arithmetic of all four instantiations (and of adam_wprep_kernel) is the one definition of adam_update.h,
 // whose roundings are written out and reproduce what the float4 loop computed before (tests/test_gpu_adam_bits.py).  The scalar
 // tail -- never run by the product: ParamArena pads every arena to 64 -- takes the loop's rounding too.
-template <bool FIX, bool GUARD = false>
+// SCHED (xmc_*_sched; libml/opt_schedule.py): lr and d are the float32 values adam_advance_sched_kernel has just left in slots 4
+// and 5 of the step state instead of the host's arguments -- two more uniform loads beside the corrections', then the same
+// AdamHyper and the same adam_update.  The SCHED = false instantiations are the kernels as they were.
+template <bool FIX, bool GUARD = false, bool SCHED = false>
 __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, float* __restrict__ g,
                                                    float* __restrict__ m, float* __restrict__ v,
                                                    float* __restrict__ ema, long long n, float lr, float b1,
@@ -200,6 +205,7 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, float*
         }
     }
     if (corr) { ic1 = corr[1]; ic2 = corr[2]; }      // device-side step counter (hipGraph replay): see adam_advance_kernel
+    if constexpr (SCHED) { lr = corr[4]; d = corr[5]; }      // this update's rate and EMA decay: see adam_advance_sched_kernel
     const AdamHyper h = {lr, b1, b2, eps, ic1, ic2, gs, d};
     const long long n4 = n >> 2;
     for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n4; i += (long long)gridDim.x * 256) {
@@ -415,6 +421,40 @@ __global__ void adam_advance_kernel(float* state, double b1, double b2, const in
     state[2] = (float)(1.0 / (1.0 - pow(b2, (double)t)));
 }
 
+// The scheduled form (xmc_*_sched): the same advance of t and of the two corrections, then this update's learning rate and EMA
+// decay from the schedule `s` -- a pure function of t and of constants, so one captured graph serves a whole run with warm-up,
+// decay and an EMA ramp.  libml/opt_schedule.evaluate is the specification: IEEE double in its order, and no multiply may fuse
+// with the add behind it (contraction is switched off for the function, as in lecam.hip).  state[4] = lr_t, state[5] = d_t,
+// state[6] = float32(w f); slots 3 and 7 are not touched.  ONE thread; a skipped half step (GUARD, verdict[0] != 0) writes nothing.
+template <bool GUARD = false>
+__global__ void adam_advance_sched_kernel(float* state, double b1, double b2, xmc_opt_schedule s, const int* verdict = nullptr) {
+#pragma clang fp contract(off)
+    if constexpr (GUARD) {
+        if (verdict[0] != 0) return;
+    }
+    const int t = __float_as_int(state[0]) + 1;
+    state[0] = __int_as_float(t);
+    state[1] = (float)(1.0 / (1.0 - pow(b1, (double)t)));
+    state[2] = (float)(1.0 / (1.0 - pow(b2, (double)t)));
+    const double td = (double)t;
+    const double w = (s.warmup > 0 && (long long)t < s.warmup) ? td / (double)s.warmup : 1.0;
+    double x;
+    if ((long long)t <= s.decay_start) x = 0.0;
+    else if ((long long)t >= s.decay_end) x = 1.0;
+    else x = (double)((long long)t - s.decay_start) / (double)(s.decay_end - s.decay_start);
+    const double r = s.final_ratio;
+    double f = 1.0;
+    if (s.kind == XMC_SCHED_LINEAR) f = 1.0 + (r - 1.0) * x;
+    else if (s.kind == XMC_SCHED_COSINE) f = r + (1.0 - r) * (0.5 * (1.0 + cos(3.141592653589793 * x)));
+    state[4] = (float)((s.base * w) * f);
+    state[6] = (float)(w * f);
+    float d;
+    if ((long long)t <= s.ema_start) d = 0.f;
+    else if (s.ema_ramp > 0.0) d = (float)fmin(s.ema_decay, (1.0 + td) / (s.ema_ramp + td));
+    else d = (float)s.ema_decay;
+    state[5] = d;
+}
+
 namespace {
 
 // What the five flat entry points below hand to launch_adam_flat, in the order of their own parameters: an entry point fills the
@@ -436,7 +476,23 @@ struct AdamFlatArgs {
     const int32_t* verdict = nullptr;
     bool host_step = false;                          // xmc_adam_ema: the caller computed c = 1 - beta^t
     float c1 = 1.f, c2 = 1.f;
+    bool scheduled = false;                          // xmc_*_sched: lr and ema_decay come from `sched` through the step state
+    const xmc_opt_schedule* sched = nullptr;
 };
+
+// the domain of a schedule descriptor (include/xmcgan_hip.h; libml/opt_schedule.Schedule.validate is the same list)
+int validate_opt_schedule(const xmc_opt_schedule* s) {
+    XMC_REQUIRE(s != nullptr);
+    XMC_REQUIRE(s->kind == XMC_SCHED_CONSTANT || s->kind == XMC_SCHED_LINEAR || s->kind == XMC_SCHED_COSINE);
+    XMC_REQUIRE(s->reserved == 0);
+    XMC_REQUIRE(std::isfinite(s->base) && s->base > 0.0);
+    XMC_REQUIRE(s->warmup >= 0 && s->decay_start >= 0 && s->decay_end >= 0 && s->ema_start >= 0);
+    XMC_REQUIRE(s->kind == XMC_SCHED_CONSTANT || s->decay_end > s->decay_start);
+    XMC_REQUIRE(std::isfinite(s->final_ratio) && s->final_ratio >= 0.0 && s->final_ratio <= 1.0);
+    XMC_REQUIRE(s->ema_decay >= 0.0 && s->ema_decay < 1.0);                 // (a NaN fails both)
+    XMC_REQUIRE(std::isfinite(s->ema_ramp) && s->ema_ramp >= 0.0);
+    return XMC_OK;
+}
 
 int validate_adam_flat(const AdamFlatArgs& a) {
     XMC_REQUIRE(a.p && a.g && a.m && a.v && a.n > 0);
@@ -444,20 +500,30 @@ int validate_adam_flat(const AdamFlatArgs& a) {
     XMC_REQUIRE(a.host_step ? (a.c1 > 0.f && a.c2 > 0.f) : a.step_state != nullptr);
     XMC_REQUIRE(!a.table || (a.map && a.n_entries > 0 && a.kvec && a.scal && a.u && a.vv));     // (map without table: skip marks only)
     XMC_REQUIRE(!a.guarded || (a.verdict && xmc_aligned(a.verdict, 4)));
+    if (a.scheduled) {
+        XMC_REQUIRE(!a.host_step);
+        if (const int rc = validate_opt_schedule(a.sched)) return rc;
+    }
     return XMC_OK;
 }
 
-// adam_kernel<FIX = a table is given, GUARD = the entry point is a guarded one>, behind adam_advance_kernel where the step lives
-// on the device
+// adam_kernel<FIX = a table is given, GUARD = the entry point is a guarded one, SCHED = a scheduled one>, behind
+// adam_advance_kernel (adam_advance_sched_kernel) where the step lives on the device
 int launch_adam_flat(const AdamFlatArgs& a) {
     if (const int rc = validate_adam_flat(a)) return rc;
     hipStream_t s = static_cast<hipStream_t>(a.stream);
     const int* verdict = a.guarded ? static_cast<const int*>(a.verdict) : nullptr;
-    if (!a.host_step)
+    if (a.scheduled)
+        hipLaunchKernelGGL(a.guarded ? adam_advance_sched_kernel<true> : adam_advance_sched_kernel<false>, dim3(1), dim3(1), 0, s,
+                           a.step_state, a.beta1, a.beta2, *a.sched, verdict);
+    else if (!a.host_step)
         hipLaunchKernelGGL(a.guarded ? adam_advance_kernel<true> : adam_advance_kernel<false>, dim3(1), dim3(1), 0, s, a.step_state,
                            a.beta1, a.beta2, verdict);
-    const auto kernel = a.table ? (a.guarded ? adam_kernel<true, true> : adam_kernel<true, false>)
-                                : (a.guarded ? adam_kernel<false, true> : adam_kernel<false, false>);
+    const auto plain = a.table ? (a.guarded ? adam_kernel<true, true> : adam_kernel<true, false>)
+                               : (a.guarded ? adam_kernel<false, true> : adam_kernel<false, false>);
+    const auto sched = a.table ? (a.guarded ? adam_kernel<true, true, true> : adam_kernel<true, false, true>)
+                               : (a.guarded ? adam_kernel<false, true, true> : adam_kernel<false, false, true>);
+    const auto kernel = a.scheduled ? sched : plain;
     hipLaunchKernelGGL(kernel, dim3(grid_for(a.n / 4 + 1)), dim3(256), 0, s, a.p, a.g, a.m, a.v, a.ema, (long long)a.n, a.lr,
                        (float)a.beta1, (float)a.beta2, a.eps, a.host_step ? 1.f / a.c1 : 1.f, a.host_step ? 1.f / a.c2 : 1.f,
                        a.grad_scale, a.ema_decay, static_cast<const float*>(a.step_state), a.zero_grads,
@@ -514,6 +580,31 @@ extern "C" int xmc_adam_ema_dev_sn_guarded(float* p, float* g, float* m, float* 
                                            const int32_t* verdict, void* stream) {
     return launch_adam_flat({p, g, m, v, ema, n, lr, beta1, beta2, eps, step_state, grad_scale, ema_decay, stream, zero_grads, map, table,
                              n_entries, kvec, scal, u, vv, true, verdict});
+}
+
+// ---- the scheduled forms (config.lr_schedule, config.ema_ramp, ...; libml/opt_schedule.py): the entry points above without `lr` and
+// `ema_decay`, which adam_advance_sched_kernel derives from `sched` and Adam's t on the device.  `verdict` may be NULL: the
+// unguarded form.
+extern "C" int xmc_adam_ema_dev_sched(float* p, const float* g, float* m, float* v, float* ema, int64_t n, double beta1, double beta2,
+                                      float eps, float* step_state, float grad_scale, const xmc_opt_schedule* sched,
+                                      const int32_t* verdict, void* stream) {
+    AdamFlatArgs a = {p, const_cast<float*>(g), m, v, ema, n, 0.f, beta1, beta2, eps, step_state, grad_scale, 0.f, stream};
+    a.guarded = verdict != nullptr;
+    a.verdict = verdict;
+    a.scheduled = true;
+    a.sched = sched;
+    return launch_adam_flat(a);
+}
+
+extern "C" int xmc_adam_ema_dev_sn_sched(float* p, float* g, float* m, float* v, float* ema, int64_t n, double beta1, double beta2,
+                                         float eps, float* step_state, float grad_scale, int32_t zero_grads, const void* map,
+                                         const void* table, int32_t n_entries, const float* kvec, const float* scal, const float* u,
+                                         const float* vv, const xmc_opt_schedule* sched, const int32_t* verdict, void* stream) {
+    AdamFlatArgs a = {p, g, m, v, ema, n, 0.f, beta1, beta2, eps, step_state, grad_scale, 0.f, stream, zero_grads, map, table,
+                      n_entries, kvec, scal, u, vv, verdict != nullptr, verdict};
+    a.scheduled = true;
+    a.sched = sched;
+    return launch_adam_flat(a);
 }
 
 // Running sums of a step's scalar metrics, kept on the device so that a replayed training graph needs no host read per step

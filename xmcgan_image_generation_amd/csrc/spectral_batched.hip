@@ -504,7 +504,8 @@ __global__ __launch_bounds__(256) void wprep_kernel(const WprepEntry* __restrict
 // and never reads the float32 masters.  The flat Adam kernel skips these tensors (map value -2).
 // GUARD (xmc_adam_wprep_tiles_guarded): verdict[0] != 0 leaves p, m, v, ema AND the emitted copies / partial rows as they are
 // (they still describe the parameters, which did not change) and only zeroes the tile's gradient where zero_g == 1 would.
-template <bool FIX, bool GUARD = false>
+// SCHED (xmc_adam_wprep_tiles_sched): lr and d are slots 4 and 5 of the step state (adam_advance_sched_kernel, pointwise.hip).
+template <bool FIX, bool GUARD = false, bool SCHED = false>
 __global__ __launch_bounds__(256) void adam_wprep_kernel(const WprepEntry* __restrict__ tab, int n, float* __restrict__ p,
                                                          float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
                                                          float* __restrict__ ema, float lr, float b1, float b2, float eps,
@@ -532,6 +533,7 @@ __global__ __launch_bounds__(256) void adam_wprep_kernel(const WprepEntry* __res
             return;
         }
     }
+    if constexpr (SCHED) { lr = corr[4]; d = corr[5]; }                  // this update's rate and EMA decay, from the schedule
     const AdamHyper h = {lr, b1, b2, eps, corr[1], corr[2], gs, d};      // device-side step counter, already advanced (adam_advance_kernel)
     const bool spectral = FIX && (e.flags & 16);
     float ur = 0.f, is = 1.f;
@@ -698,6 +700,7 @@ struct AdamTilesArgs {
     void* stream;
     bool guarded = false;
     const int32_t* verdict = nullptr;
+    bool scheduled = false;                          // xmc_adam_wprep_tiles_sched: lr and ema_decay are read from step_state
 };
 
 int validate_adam_tiles(const AdamTilesArgs& a) {
@@ -709,11 +712,14 @@ int validate_adam_tiles(const AdamTilesArgs& a) {
     return XMC_OK;
 }
 
-// adam_wprep_kernel<FIX = kvec is given, GUARD = the entry point is the guarded one>
+// adam_wprep_kernel<FIX = kvec is given, GUARD = the entry point is the guarded one, SCHED = the scheduled one>
 int launch_adam_tiles(const AdamTilesArgs& a) {
     if (const int rc = validate_adam_tiles(a)) return rc;
-    const auto kernel = a.kvec ? (a.guarded ? adam_wprep_kernel<true, true> : adam_wprep_kernel<true, false>)
-                               : (a.guarded ? adam_wprep_kernel<false, true> : adam_wprep_kernel<false, false>);
+    const auto plain = a.kvec ? (a.guarded ? adam_wprep_kernel<true, true> : adam_wprep_kernel<true, false>)
+                              : (a.guarded ? adam_wprep_kernel<false, true> : adam_wprep_kernel<false, false>);
+    const auto sched = a.kvec ? (a.guarded ? adam_wprep_kernel<true, true, true> : adam_wprep_kernel<true, false, true>)
+                              : (a.guarded ? adam_wprep_kernel<false, true, true> : adam_wprep_kernel<false, false, true>);
+    const auto kernel = a.scheduled ? sched : plain;
     hipLaunchKernelGGL(kernel, dim3(a.blocks), dim3(256), 0, static_cast<hipStream_t>(a.stream), static_cast<const WprepEntry*>(a.table),
                        a.n, a.p, a.g, a.m, a.v, a.ema, a.lr, (float)a.beta1, (float)a.beta2, a.eps, a.step_state, a.grad_scale,
                        a.ema_decay, a.zero_grads, a.kvec, a.scal, a.u, a.vv, static_cast<bf16_t*>(a.wf_buf),
@@ -746,6 +752,19 @@ extern "C" int xmc_adam_wprep_tiles_guarded(const void* table, int32_t n, int32_
                                             float* part, const int32_t* verdict, void* stream) {
     return launch_adam_tiles({table, n, blocks, p, g, m, v, ema, lr, beta1, beta2, eps, step_state, grad_scale, ema_decay, zero_grads,
                               kvec, scal, u, vv, wf_buf, wd_buf, pf_buf, pd_buf, part, stream, true, verdict});
+}
+
+// xmc_adam_wprep_tiles on a step_state that xmc_adam_ema_dev_sn_sched advanced: this update's lr and EMA decay are its slots 4 and 5
+// (libml/opt_schedule.py).  `verdict` may be NULL: the unguarded form.
+extern "C" int xmc_adam_wprep_tiles_sched(const void* table, int32_t n, int32_t blocks, float* p, float* g, float* m, float* v,
+                                          float* ema, double beta1, double beta2, float eps, const float* step_state,
+                                          float grad_scale, int32_t zero_grads, const float* kvec, const float* scal, const float* u,
+                                          const float* vv, void* wf_buf, void* wd_buf, void* pf_buf, void* pd_buf, float* part,
+                                          const int32_t* verdict, void* stream) {
+    AdamTilesArgs a = {table, n, blocks, p, g, m, v, ema, 0.f, beta1, beta2, eps, step_state, grad_scale, 0.f, zero_grads,
+                       kvec, scal, u, vv, wf_buf, wd_buf, pf_buf, pd_buf, part, stream, verdict != nullptr, verdict};
+    a.scheduled = true;
+    return launch_adam_tiles(a);
 }
 
 // Power iteration whose first matvec arrives as partial rows from xmc_wprep_batched for the `wtab` entries (`part`); the

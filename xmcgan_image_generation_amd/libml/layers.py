@@ -117,9 +117,10 @@ class ParamArena:
         self.v = ops.zeros((self.size,)) if with_opt else None
         # Adam step counter: the kernels read it from DEVICE memory (``step_state``: [t as int32 bits, 1/(1-b1^t),
         # 1/(1-b2^t), pad], advanced by xmc_adam_ema_dev) so that a captured hipGraph replays consecutive steps;
-        # ``opt_step`` is the host mirror (checkpoints, flax ``state.step``).
+        # ``opt_step`` is the host mirror (checkpoints, flax ``state.step``).  Slots 4 .. 7 ([lr_t, d_t, w f, pad]) belong to the
+        # scheduled forms (libml/opt_schedule.py): this update's learning rate and EMA decay, evaluated on the device from t.
         self._opt_step = 0
-        self.step_state = (torch.zeros((4,), dtype=torch.float32, device=self.params.device)
+        self.step_state = (torch.zeros((8,), dtype=torch.float32, device=self.params.device)
                            if with_opt and hasattr(ops, "adam_ema_dev") else None)
         self.version = 0         # bumped whenever params change (invalidates prepared weights)
         # True while the gradient arena is known to be all zeros: the fused optimiser kernel (ops.adam_ema_dev_sn) zeroes

@@ -1641,12 +1641,22 @@ class HipOps:
             m[e["w_off"] // align:(e["w_off"] + e["cout"] * e["taps"] * e["cin"]) // align] = -2
         return m.to(self.device)
 
-    def _adam(self, name, *args, verdict=None):
+    def _adam(self, name, *args, verdict=None, schedule=None):
         """The one call site of the optimiser entry points: ``name(*args, stream)`` or, with a ``verdict``
-        (config.skip_nonfinite_updates), its ``_guarded`` form, which takes the verdict in front of the stream"""
-        if verdict is not None:
+        (config.skip_nonfinite_updates), its ``_guarded`` form, which takes the verdict in front of the stream; with a
+        ``schedule`` (libml/opt_schedule.Schedule, or True for the tile form, which only reads the step state) its ``_sched``
+        form, which takes the descriptor and a nullable verdict there -- ``args`` then come without ``lr`` and ``ema_decay``"""
+        if schedule is not None:
+            desc = () if schedule is True else (C.byref(_lib.OptSchedule(**vars(schedule))),)     # (read during the call)
+            name, args = name + "_sched", (*args, *desc, _p(verdict))
+        elif verdict is not None:
             name, args = name + "_guarded", (*args, _p(verdict))
         check(getattr(self.lib, name)(*args, self._stream()), name)
+
+    @staticmethod
+    def _sched_state(step_state):
+        """a scheduled form writes (reads) slots 4 .. 6 of the step state: ``ParamArena`` allocates the 8"""
+        assert step_state.dtype == torch.float32 and step_state.numel() >= 8 and step_state.is_contiguous()
 
     def _zero_g(self, zero_grads):
         """the kernels' zero_g argument -- 0: the consumed gradient stays, 1: it is zeroed, 2 (``keep_grads``): the FINAL gradient
@@ -1670,15 +1680,47 @@ class HipOps:
         ``verdict`` (config.skip_nonfinite_updates): the guarded form -- verdict[0] != 0 leaves everything but the gradient alone.
         Returns True where the gradient arena is all zeros again."""
         assert step_state.dtype == torch.float32 and step_state.numel() >= 4
-        if fix is not None:
-            mp, bank, kvec, scal, u, vv = fix
-            sn = (_p(mp), _p(bank["tab_fix"]), bank["n"], _p(kvec), _p(scal), _p(u), _p(vv))
-        else:
-            sn = (_p(skip_map), None, 0, None, None, None, None)
         zero_g = self._zero_g(zero_grads)
         self._adam("xmc_adam_ema_dev_sn", _p(p), _p(g), _p(m), _p(v), _p(ema), p.numel(), lr, beta1, beta2, eps, _p(step_state),
-                   grad_scale, ema_decay, zero_g, *sn, verdict=verdict)
+                   grad_scale, ema_decay, zero_g, *self._sn_args(fix, skip_map), verdict=verdict)
         return zero_g == 1
+
+    @staticmethod
+    def _sn_args(fix, skip_map):
+        """map, table, n_entries, kvec, scal, u, vv of xmc_adam_ema_dev_sn"""
+        if fix is not None:
+            mp, bank, kvec, scal, u, vv = fix
+            return (_p(mp), _p(bank["tab_fix"]), bank["n"], _p(kvec), _p(scal), _p(u), _p(vv))
+        return (_p(skip_map), None, 0, None, None, None, None)
+
+    # ---- the scheduled forms (libml/opt_schedule.py): the learning rate and the EMA decay of each update are evaluated on the
+    # device from Adam's own t and ``schedule`` (an ``opt_schedule.Schedule``), and travel through slots 4 .. 6 of ``step_state``
+    # (8 float32) -- no ``lr`` / ``ema_decay`` argument that a captured graph would freeze.  ``verdict``: the guarded behaviour.
+    def adam_ema_dev_sched(self, p, g, m, v, ema, step_state, schedule, *, beta1, beta2, eps=1e-8, grad_scale=1.0, verdict=None):
+        """``adam_ema_dev`` with its rate and EMA decay from ``schedule``"""
+        self._sched_state(step_state)
+        self._adam("xmc_adam_ema_dev", _p(p), _p(g), _p(m), _p(v), _p(ema), p.numel(), beta1, beta2, eps, _p(step_state), grad_scale,
+                   verdict=verdict, schedule=schedule)
+
+    def adam_ema_dev_sn_sched(self, p, g, m, v, ema, step_state, schedule, *, beta1, beta2, eps=1e-8, grad_scale=1.0, zero_grads=True,
+                              fix=None, skip_map=None, verdict=None):
+        """``adam_ema_dev_sn`` with its rate and EMA decay from ``schedule``.  Returns True where the gradient arena is all zeros
+        again."""
+        self._sched_state(step_state)
+        zero_g = self._zero_g(zero_grads)
+        self._adam("xmc_adam_ema_dev_sn", _p(p), _p(g), _p(m), _p(v), _p(ema), p.numel(), beta1, beta2, eps, _p(step_state), grad_scale,
+                   zero_g, *self._sn_args(fix, skip_map), verdict=verdict, schedule=schedule)
+        return zero_g == 1
+
+    def adam_wprep_sched(self, wp, out, p, g, m, v, ema, step_state, *, beta1, beta2, eps=1e-8, grad_scale=1.0, zero_grads=True,
+                         fix=None, verdict=None):
+        """``adam_wprep`` on a ``step_state`` that ``adam_ema_dev_sn_sched`` has already advanced for this update: the rate and the
+        EMA decay are the ones it left there"""
+        self._sched_state(step_state)
+        bufs, part = out
+        self._adam("xmc_adam_wprep_tiles", _p(wp["tab"]), wp["n"], wp["blocks"], _p(p), _p(g), _p(m), _p(v), _p(ema), beta1, beta2, eps,
+                   _p(step_state), grad_scale, self._zero_g(zero_grads), *[_p(t) for t in (fix or (None,) * 4)],
+                   *[_p(b) for b in bufs], _p(part), verdict=verdict, schedule=True)
 
     # ---------------------------------------------------------------------------------- optimiser
     def adam_ema(self, p, g, m, v, ema, *, lr, beta1, beta2, step, eps=1e-8, grad_scale=1.0, ema_decay=0.0):

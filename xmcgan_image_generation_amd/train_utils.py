@@ -92,6 +92,8 @@ def create_train_state(config, rng, init_batch=None, ops=None):
     ada_lib.check_config(config)                     # config.ada_target: a policy to gate, settings inside their domains
     from .libml import lecam as lecam_lib
     lecam_lib.check_config(config)                   # config.lecam_weight / _decay / _start: inside their domains
+    from .libml import opt_schedule
+    opt_schedule.check_config(config)                # config.lr_schedule / lr_* / ema_ramp / ema_start_step: inside their domains
     ops = ops if ops is not None else xmc_net.make_ops(dtype)
     if config.get("conv_fp8", False):                # BASELINE config #5: MX-fp8 3x3 convolutions (ops.py::_conv_mx8)
         if dtype != torch.bfloat16:
@@ -568,6 +570,30 @@ def _array_fields(batch):
     return {k: torch.as_tensor(v) for k, v in batch.items() if isinstance(v, (torch.Tensor, np.ndarray))}
 
 
+def optimizer_rates(state, config):
+    """With a schedule (libml/opt_schedule.py): the learning rates and the EMA decay of the optimisers' last updates ->
+    ``{"opt/g_lr", "opt/d_lr", "opt/ema_decay"}``.  Read from slots 4 and 5 of the arenas' ``step_state``, where the scheduled
+    advance kernel left them (a host synchronisation: ``train`` calls it where it reads the metric sums anyway); on an operator
+    table without a device counter, the specification at the host's t.  Before the first update every value is 0."""
+    from .libml import opt_schedule
+    out = {}
+    for role, opt in (("g", state.g_optimizer), ("d", state.d_optimizer)):
+        a = opt.arena
+        if a.step_state is not None:
+            now = opt_schedule.read_slots(a.step_state)
+            lr, decay = now["lr"], now["ema_decay"]
+        elif a.opt_step < 1:
+            lr = decay = 0.0
+        else:
+            ema = role == "g" and config.get("ema", True)
+            s = opt_schedule.for_optimizer(config, role, config.g_lr if role == "g" else config.d_lr, config.polyak_decay if ema else 0.0)
+            lr, decay = (float(x) for x in opt_schedule.evaluate(s, a.opt_step)[:2])
+        out[f"opt/{role}_lr"] = lr
+        if role == "g":
+            out["opt/ema_decay"] = decay
+    return out
+
+
 def check_replica_drift(states, grad_sync):
     """The tripwire of DESIGN.md 9f.3: ``states`` maps a controller's name to its small device state (float64[8] / int32[4]; None =
     the switch is off), which every replica must hold BIT FOR BIT -- rank 0's checkpoint is then everybody's.  The states are
@@ -620,6 +646,9 @@ def train(config, workdir, test_mode=False, *, datasets=None):
     train_iter, _eval_iter, num_train_examples = (datasets or default_datasets)(config, streams["data"], initial_step, rank, world,
                                                                                  device)
     num_train_steps = resolve_num_train_steps(config, num_train_examples, int(os.environ.get("LOCAL_WORLD_SIZE", world)), test_mode)
+    from .libml import opt_schedule
+    config = opt_schedule.resolve(config, num_train_steps)     # a decaying schedule without lr_decay_end_step ends with the run
+    scheduled = opt_schedule.enabled(config)
     grad_sync = None
     if distributed:
         from .dp import GradSync
@@ -707,6 +736,7 @@ def train(config, workdir, test_mode=False, *, datasets=None):
                                      f"written (the newest one is {rotation.latest()}){where}")
         ada_now = ada.read() if ada is not None else None         # (with the accumulator too: the stream is already drained)
         lecam_now = lecam.read() if lecam is not None else None   # (likewise)
+        rates_now = optimizer_rates(state, config) if scheduled else None      # (likewise: the two step states)
         state = xmc_gan._flush(state)
         if write_scalars:
             # (a window whose every step was skipped has no metric to average: NaN, as 0 / 0 says)
@@ -721,6 +751,8 @@ def train(config, workdir, test_mode=False, *, datasets=None):
             if lecam_now is not None:
                 scalars.update({"lecam/anchor_real": lecam_now["anchor_real"], "lecam/anchor_fake": lecam_now["anchor_fake"],
                                 "lecam/updates": lecam_now["updates"]})
+            if rates_now is not None:                # the rates of the LAST update of the window, as the kernels read them
+                scalars.update(rates_now)
             if statistics is not None:               # this replica's statistics (not averaged over replicas): window means
                 window = statistics.read()
                 if writes:

@@ -28,6 +28,7 @@ from .libml import diff_augment
 from .libml import lecam as lecam_lib
 from .libml import losses
 from .libml import nonfinite_guard
+from .libml import opt_schedule
 from .nets import xmc_net
 from .utils import pretrained_model_utils
 
@@ -525,10 +526,15 @@ def _judge(ops, guard, d, segments, u_new, replicas=None):
     return guard.judge(ops, segments, replicas=replicas)
 
 
-def _apply_adam(ops, opt, config, lr, grad_scale, ema=None, fix_args=None, net=None, stats=None, verdict=None, fresh_u=None):
+def _apply_adam(ops, opt, config, lr, grad_scale, ema=None, fix_args=None, net=None, stats=None, verdict=None, fresh_u=None, *,
+                role):
     """flax.optim.Adam.apply_gradient (+ EMA).  ``fix_args`` (Discriminator.sn_fix_args()): the gradient through sigma of the
     spectrally-normalised weights rides in the optimiser kernel -- its scalar <G, W> is formed HERE, on the gradient the
     update consumes (after the replicas' exchange: the term is linear in G, and u, v, sigma are identical on every replica).
+    ``role``: "d" | "g", whose optimiser this is.  With a schedule (libml/opt_schedule.py: config.lr_schedule, config.ema_ramp,
+    ...) ``lr`` and ``config.polyak_decay`` are BASE values, and the rate and the EMA decay of this update are a function of
+    Adam's own t: evaluated on the device by the scheduled forms of the kernels (a captured graph replays the right ones), on the
+    host where Adam's t is the host's.
     ``net`` (the Generator / Discriminator that owns the arena; round 5, ops.fuse_prep): the update of its batched-preparation
     weights also EMITS their prepared copies for the next forward pass (xmc_adam_wprep_tiles).
     ``stats`` = (TrainStatistics, "d" | "g") (train_g_d's own updates only): the per-tensor sums of squares of the gradient this
@@ -551,25 +557,44 @@ def _apply_adam(ops, opt, config, lr, grad_scale, ema=None, fix_args=None, net=N
     if getattr(a, "first_write", False):
         a.audit_writes()                     # (first update only) every leaf of the arena was written by this half step
     prep = None
+    sched = opt_schedule.for_optimizer(config, role, lr, decay)      # (None: the feature is off; host-side, eager or capture only)
+    if sched is not None and a.step_state is None:
+        # no device-side step counter: Adam's t is the host's (just advanced), and so is the schedule -- plain floats from here on
+        lr_t, d_t, _ = opt_schedule.evaluate(sched, a.opt_step)
+        lr, decay, sched = float(lr_t), float(d_t) if ema is not None else 0.0, None
+
+    def form(name, descriptor=True):
+        """-> (the operator ``name`` or its scheduled form, the keywords that carry this update's rate and EMA decay)"""
+        if sched is None:
+            return getattr(ops, name), dict(lr=lr, ema_decay=decay)
+        fn = getattr(ops, name + "_sched", None)
+        if fn is None:
+            raise ValueError(f"config asks for a learning-rate / EMA schedule ({', '.join(k for k in opt_schedule.KEYS if k in config)}) "
+                             f"and the operator table keeps Adam's step on the device ({name}) but has no {name}_sched: the "
+                             "rate would silently stay constant")
+        return fn, (dict(schedule=sched) if descriptor else {})
     if a.step_state is not None and getattr(ops, "fuse_opt", False):
         if net is not None and getattr(ops, "fuse_prep", False) and hasattr(net, "adam_prep"):
             prep = net.adam_prep(a)
+        adam_sn, rate_sn = form("adam_ema_dev_sn")
+        adam_tiles, rate_tiles = form("adam_wprep", descriptor=False) if prep is not None else (None, None)
         fix = kvec = None
         if fix_args is not None:
             mp, bank, scal, u, v = fix_args
             kvec = ops.sn_bank_dot(bank, a.params, a.grads, scal)
             fix = (prep["skip_map"] if prep is not None else mp, bank, kvec, scal, u, v)
         zero = not getattr(a, "first_write", False)
-        a.grads_clean = ops.adam_ema_dev_sn(a.params, a.grads, a.m, a.v, ema, a.step_state, lr=lr, beta1=config.beta1,
-                                            beta2=config.beta2, grad_scale=grad_scale, ema_decay=decay, fix=fix, zero_grads=zero,
-                                            **({"skip_map": prep["skip_map"]} if prep is not None and fix is None else {}), **guard_kw)
+        a.grads_clean = adam_sn(a.params, a.grads, a.m, a.v, ema, a.step_state, beta1=config.beta1,
+                                beta2=config.beta2, grad_scale=grad_scale, fix=fix, zero_grads=zero, **rate_sn,
+                                **({"skip_map": prep["skip_map"]} if prep is not None and fix is None else {}), **guard_kw)
         if prep is not None:                 # ... and the tensors that kernel skipped: update + prepared copies in one pass
-            ops.adam_wprep(prep["wp"], prep["out"], a.params, a.grads, a.m, a.v, ema, a.step_state, lr=lr, beta1=config.beta1,
-                           beta2=config.beta2, grad_scale=grad_scale, ema_decay=decay, zero_grads=zero,
-                           fix=(kvec, fix_args[2], fix_args[3], fix_args[4]) if fix_args is not None else None, **guard_kw)
+            adam_tiles(prep["wp"], prep["out"], a.params, a.grads, a.m, a.v, ema, a.step_state, beta1=config.beta1,
+                       beta2=config.beta2, grad_scale=grad_scale, zero_grads=zero, **rate_tiles,
+                       fix=(kvec, fix_args[2], fix_args[3], fix_args[4]) if fix_args is not None else None, **guard_kw)
     elif a.step_state is not None:          # device-side step counter (hipGraph-replayable)
-        ops.adam_ema_dev(a.params, a.grads, a.m, a.v, ema, a.step_state, lr=lr, beta1=config.beta1,
-                         beta2=config.beta2, grad_scale=grad_scale, ema_decay=decay, **guard_kw)
+        adam_dev, rate = form("adam_ema_dev")
+        adam_dev(a.params, a.grads, a.m, a.v, ema, a.step_state, beta1=config.beta1,
+                 beta2=config.beta2, grad_scale=grad_scale, **rate, **guard_kw)
     else:
         ops.adam_ema(a.params, a.grads, a.m, a.v, ema, lr=lr, beta1=config.beta1, beta2=config.beta2,
                      step=a.opt_step, grad_scale=grad_scale, ema_decay=decay)
@@ -676,7 +701,7 @@ def train_d(rng, state, batch, generator, discriminator, config, grad_sync=None,
 
             def finish():
                 grad_sync.wait("d")
-                _apply_adam(ops, opt, config, config.d_lr, scale, fix_args=fix_args, net=d)
+                _apply_adam(ops, opt, config, config.d_lr, scale, fix_args=fix_args, net=d, role="d")
             return state.replace(discriminator_state={"spectral_norm_stats": new_sn}, pending=finish)
         grad_sync.wait("d")
     if do_prefetch and prefetched is None:
@@ -687,10 +712,10 @@ def train_d(rng, state, batch, generator, discriminator, config, grad_sync=None,
         # (G's new running statistics are discarded as always, but they are scanned: a NaN the generator's forward pass met
         # shows in its batch statistics even where a max(x, 0) further on turned it into a finite, meaningless image)
         verdict = _judge(ops, guard, d, [d_arena.grads, new_sn.flat, _new_g_stats.flat], new_sn.flat, replicas=grad_sync)
-        _apply_adam(ops, state.d_optimizer, config, config.d_lr, scale, fix_args=fix_args, net=d, verdict=verdict, fresh_u=u0)
+        _apply_adam(ops, state.d_optimizer, config, config.d_lr, scale, fix_args=fix_args, net=d, verdict=verdict, fresh_u=u0, role="d")
         guard.commit(ops, u0, new_sn.flat)
         return state.replace(prefetched_g=prefetched)
-    _apply_adam(ops, state.d_optimizer, config, config.d_lr, scale, fix_args=fix_args, net=d)
+    _apply_adam(ops, state.d_optimizer, config, config.d_lr, scale, fix_args=fix_args, net=d, role="d")
     # G's new batch_stats are discarded (xmc_gan.py:231); D's new u0 are kept (:253-255)
     return state.replace(discriminator_state={"spectral_norm_stats": new_sn}, prefetched_g=prefetched)
 
@@ -796,7 +821,7 @@ def train_g_d(rng, state, batch, generator, discriminator, config, additional_da
             # instead of after the join
             ops.wait_event(d_part_done)
             _apply_adam(ops, state.d_optimizer, config, config.d_lr, d_scale, fix_args=_fix_args(d), net=d,
-                        stats=(stats, "d") if stats is not None else None)
+                        stats=(stats, "d") if stats is not None else None, role="d")
             d_updated = True
         ops.join_side()
         if excl:
@@ -856,12 +881,12 @@ def _finish_g_d(ops, state, config, out, c_pre, new_g_stats, new_sn, d_scale, g_
         kw_d, kw_g = dict(verdict=verdict, fresh_u=u0), dict(verdict=verdict)
     if not d_updated:
         _apply_adam(ops, state.d_optimizer, config, config.d_lr, d_scale, fix_args=fix_args, net=nets[1],
-                    stats=(stats, "d") if stats is not None else None, **kw_d)
+                    stats=(stats, "d") if stats is not None else None, role="d", **kw_d)
     if grad_sync is not None:
         grad_sync.wait("g")
     ema = state.ema_buffer if config.get("ema", True) else None
     _apply_adam(ops, state.g_optimizer, config, config.g_lr, g_scale, ema, net=nets[0],      # + EMA, xmc_gan.py:174-177
-                stats=(stats, "g") if stats is not None else None, **kw_g)
+                stats=(stats, "g") if stats is not None else None, role="g", **kw_g)
     if stats is not None:
         stats.finish(ops)
     if guard is not None:                    # the state keeps its flat buffers; the batch was consumed: state.step advances
