@@ -546,11 +546,13 @@ def test_pointwise_dual_source_data_gradient_vs_float64(blk):
     assert float(margin.abs().max()) == 0.0
 
 
-@pytest.mark.parametrize("switch", ["_RESNET_BWD_MAIN", "_RESNET_REAL_EARLY", "_RESNET_SPLIT", "_RESNET_FWD_PREFETCH"])
+@pytest.mark.parametrize("switch", ["_OVERLAP_BWD", "_PREFETCH_G", "_OVERLAP_PREP"])
 def test_resnet_schedule_switches_do_not_change_the_step(switch, monkeypatch):
-    """The A/B schedule switches of the ResNet-50 term (where its pullback runs; its real half issued at the start of the step; the two
-    halves as two passes) move launches between streams / batches, never the math: eager and graph-replayed metrics of a C1-network
-    step at batch 8 equal the default schedule's to bf16 launch-shape noise, parameters after the step likewise."""
+    """The single-GPU schedule switches that remain (the two pullbacks beside each other, with the ResNet-50 pullback on the main
+    stream; the generator forward prefetched from train_d; D's preparation on the side stream), each turned off against the default,
+    move launches between streams, never the math -- which also pins the serial schedule of bench.py's instrumented step to the
+    product schedule with the ResNet-50 term on: eager and graph-replayed metrics of a C1-network step at batch 8 equal the default
+    schedule's to bf16 launch-shape noise, parameters after the step likewise."""
     from xmcgan_image_generation_amd import synthetic as syn
     from xmcgan_image_generation_amd import train_utils, xmc_gan
     from xmcgan_image_generation_amd.configs import coco_xmc

@@ -327,6 +327,52 @@ def test_discriminator_exchange_is_bucketed_only_when_the_sigma_term_follows_it(
     assert sent() and s.calls == [(40, "d", False), (40, "d", True), (20, "d", True)]
 
 
+def test_tensors_of_follows_the_twins_hung_on_a_tensor():
+    """xmc_net._tensors_of (what ``join_side`` marks for the joining stream): the ReLU-mask bits a convolution epilogue attaches
+    as ``t.bits`` and the MX-fp8 copy in ``t.mx8`` are allocated on the producing stream as well -- returned with their owner, at
+    the top level and inside a nested tape."""
+    y, plain = torch.zeros((2, 4)), torch.ones((3,))
+    y.bits = torch.zeros((2,), dtype=torch.int16)
+    assert [id(t) for t in xmc_net._tensors_of(y)] == [id(y), id(y.bits)]
+    q = torch.zeros((5,))
+    q.mx8 = (torch.zeros((5, 80), dtype=torch.uint8), "relu")
+    tape = {"blocks": [(plain, {"mask": y}), None], "b": 2, "q": (q,)}
+    assert [id(t) for t in xmc_net._tensors_of(tape)] == [id(plain), id(y), id(y.bits), id(q), id(q.mx8[0])]
+
+
+def test_wgrad_async_region_restores_the_setting_when_its_body_raises():
+    """xmc_gan._wgrad_async: the operator table's ``wgrad_async`` holds the asked value inside the region and the previous one behind
+    it -- also behind an exception from a backward pass, which used to leave the table with the region's setting for the next step."""
+    class Table:
+        wgrad_async = False
+    ops = Table()
+    with pytest.raises(RuntimeError):
+        with xmc_gan._wgrad_async(ops, True):
+            assert ops.wgrad_async is True
+            raise RuntimeError("a launch failed")
+    assert ops.wgrad_async is False
+    ops.wgrad_async = True
+    with xmc_gan._wgrad_async(ops, False):
+        assert ops.wgrad_async is False
+    assert ops.wgrad_async is True
+    with xmc_gan._wgrad_async(ops, None):                    # (None: the region keeps the table's own setting)
+        assert ops.wgrad_async is True
+    with xmc_gan._wgrad_async(object(), True):               # (a table without the attribute is left alone)
+        pass
+
+
+def test_removed_schedule_switches_are_gone_for_good():
+    """The ten schedule variants removed with their switches: a tool or test that still patches one must fail loudly, not
+    silently measure the default -- ``train_d`` has no ``next_image_model`` any more and ``xmc_gan`` none of the attributes."""
+    with pytest.raises(TypeError, match="next_image_model"):
+        xmc_gan.train_d(0, None, {}, None, None, None, next_image_model=None)
+    removed = ("_PREFETCH_AT_ADAM", "_PREFETCH_AT_START", "_PREFETCH_EARLY", "_ASYNC_WGRAD_D", "_FP8_OVERLAP", "_RESNET_BWD_MAIN",
+               "_RESNET_FWD_PREFETCH", "_RESNET_REAL_EARLY", "_RESNET_SPLIT", "_EARLY_ADAM_D")
+    assert [name for name in removed if hasattr(xmc_gan, name)] == []
+    for kept in ("_OVERLAP_BWD", "_PREFETCH_G", "_OVERLAP_PREP", "_DP_OVERLAP", "_BUCKET_D"):
+        assert isinstance(getattr(xmc_gan, kept), bool)
+
+
 def test_discriminator_arena_follows_the_tree_order_the_bucketed_exchange_assumes():
     """round-4 advisor finding: backward_d's on_ready slices assume the arena layout [DiscOptimizedBlock_0, DiscBlock_0 .. n,
     SpectralDense_0, SpectralDense_1, SpectralConv_0]; the discriminator checks it at build time (``bucket_order_ok``) and falls

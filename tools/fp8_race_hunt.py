@@ -1,6 +1,6 @@
 """Two runs of two MX-fp8 training steps from the same state: are the losses bit-identical?  (a stream race of the
 fp8 mode's overlapped schedule; the environment selects the schedule and the XMC_FP8_DEBUG bits under test.)
-    XMC_FP8_OVERLAP=1 XMC_PREFETCH_G=1 XMC_OVERLAP_BWD=0 XMC_OVERLAP_PREP=0 python tools/fp8_race_hunt.py [--config c3 --batch 32]"""
+    XMC_PREFETCH_G=1 XMC_OVERLAP_BWD=0 XMC_OVERLAP_PREP=0 python tools/fp8_race_hunt.py [--config c3 --batch 32]"""
 import argparse
 import os
 import sys

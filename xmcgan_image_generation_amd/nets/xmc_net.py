@@ -26,10 +26,14 @@ _HEADS_2STREAM = __import__("os").environ.get("XMC_HEADS_2STREAM", "0") != "0"
 
 
 def _tensors_of(obj, out=None):
-    """every tensor inside a nest of tuples / lists / dicts (a loss tape): for ops.join_side's record_stream"""
+    """every tensor inside a nest of tuples / lists / dicts (a loss tape), with the twins a convolution epilogue hung on its output
+    as attributes (``t.bits``: the ReLU-mask bits; ``t.mx8``: the MX-fp8 copy and its kind): for ops.join_side's record_stream"""
     out = [] if out is None else out
-    if torch.is_tensor(obj):
+    if isinstance(obj, torch.Tensor):
         out.append(obj)
+        for twin in (getattr(obj, "bits", None), getattr(obj, "mx8", None)):
+            if twin is not None:                     # (most tensors carry none: no call for them, this runs ~300 times a step)
+                _tensors_of(twin, out)
     elif isinstance(obj, dict):
         for v in obj.values():
             _tensors_of(v, out)

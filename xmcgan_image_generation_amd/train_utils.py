@@ -166,11 +166,6 @@ def train_step(rng, state, batch, gan_model=xmc_gan, generator=None, discriminat
         for part, rows in zip(parts, torch.chunk(host, n, dim=0)):
             part["d_aug_host"] = rows
     rngs = [int(rng) * n + i for i in range(n)]      # one stream per half step (train_utils.py:121 splits the key)
-    if (gan_model is xmc_gan and xmc_gan._RESNET_REAL_EARLY and grad_sync is None and n > 1 and additional_data
-            and additional_data.get("image_model") is not None and config.get("pretrained_image_contrastive", False)):
-        ops = generator(train=True).ops
-        if hasattr(ops, "side") and ops.dtype == torch.bfloat16:
-            xmc_gan.prefetch_pretrained_real(additional_data["image_model"], parts[-1], ops)
     for i in range(n - 1):
         # with replicas, train_d leaves its gradient exchange in flight: the D update is applied by the next half
         # step right before it first needs the D parameters (after train_g_d's generator forward)
@@ -178,8 +173,6 @@ def train_step(rng, state, batch, gan_model=xmc_gan, generator=None, discriminat
         if i == n - 2 and grad_sync is None and gan_model is xmc_gan:
             kw["next_g_batch"] = parts[-1]           # its generator forward runs beside this half step's backward
             kw["next_g_rng"] = rngs[-1]
-            if additional_data and config.get("pretrained_image_contrastive", False):
-                kw["next_image_model"] = additional_data.get("image_model")
         state = gan_model.train_d(rngs[i], state, parts[i], generator, discriminator, config, grad_sync=grad_sync,
                                   defer_update=grad_sync is not None, **kw)
     return gan_model.train_g_d(rngs[-1], state, parts[-1], generator, discriminator, config, additional_data or {},
