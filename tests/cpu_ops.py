@@ -9,8 +9,11 @@ path has no CPU fallback.
 """
 from __future__ import annotations
 
+import numpy as np
 import torch
 import torch.nn.functional as F
+
+from xmcgan_image_generation_amd.libml import ada, diff_augment, lecam, nonfinite_guard
 
 
 class CpuOps:
@@ -394,6 +397,56 @@ class CpuOps:
         p -= lr * (m / (1 - beta1 ** step)) / (torch.sqrt(v / (1 - beta2 ** step)) + eps)
         if ema is not None:
             ema.copy_(ema * ema_decay + (1 - ema_decay) * p)
+
+    # ------------------------------------------- config.diff_augment, ada_target, lecam_weight, skip_nonfinite_updates
+    # (moved here from the product package, which once carried them as the arms for "a table without the op": the torch
+    # executors of the augmentation, the torch gate, the NumPy specifications behind host reads, the guard's torch rule)
+    def diff_augment(self, real, fake, plan, plan_host, flags):
+        diff_augment.check_plan(plan_host, *fake.shape[1:3])                 # (the library's checks, for the torch executors)
+        return diff_augment.apply_torch(torch.cat([real, fake], dim=0), plan, flags)
+
+    def diff_augment_bwd(self, g, plan, plan_host, flags):
+        return diff_augment.adjoint_torch(g, plan, flags)
+
+    def ada_gate(self, aug, u, state):
+        on = (u.double() < state[0].to(u.device))[..., list(ada.PART_OF_COLUMN)]
+        ident = torch.tensor(diff_augment.IDENTITY_ROW, dtype=torch.float32, device=aug.device)
+        rows = torch.where(on, aug, ident)
+        return rows.transpose(0, 1).reshape(2 * aug.shape[0], diff_augment.PLAN_WIDTH).contiguous()
+
+    def ada_update_rows(self, rows, b, state, target, images_to_full, interval, p_max):
+        new = ada.update_rows(state.cpu().numpy(), rows.float().cpu().numpy(), b, target, images_to_full, interval, p_max)
+        state.copy_(torch.from_numpy(new))
+
+    def lecam_rows(self, rows, rank, dld, b, state, lam, decay, start, one_sided):
+        new, grad, r = lecam.step_rows(state.cpu().numpy(), rows.float().cpu().numpy(), rank, dld.detach().float().cpu().numpy(),
+                                       lam, decay, start, one_sided)
+        state.copy_(torch.from_numpy(new))
+        dld.copy_(torch.from_numpy(grad))
+        return torch.from_numpy(np.asarray([r], np.float32)).to(dld.device)
+
+    def nonfinite_verdict_ws_bytes(self, lengths):
+        return 16
+
+    def nonfinite_verdict(self, segments, verdict, counters, ws):
+        bad, first = 0, -1
+        for i, t in enumerate(segments):
+            k = int((~torch.isfinite(t)).sum())
+            if k and first < 0:
+                first = i
+            bad += k
+        verdict.copy_(torch.tensor([int(bad > 0), min(bad, nonfinite_guard._INT32_MAX), first, 0], dtype=torch.int32))
+        counters.copy_(torch.tensor(nonfinite_guard.advance_counters(counters.tolist(), bad), dtype=torch.int32))
+
+    def verdict_merge(self, rows, verdict, counters):
+        v, c = nonfinite_guard.merge_rows(rows.cpu().numpy(), counters.tolist())
+        verdict.copy_(torch.tensor(v, dtype=torch.int32))
+        counters.copy_(torch.tensor(c, dtype=torch.int32))
+
+    def commit_if(self, dst, src, verdict):
+        if int(verdict[0]) == 0:
+            dst.copy_(src)
+        return dst
 
 
 # ------------------------------------------------------------ frozen ResNet-50 feature path (canvases), torch-CPU mock

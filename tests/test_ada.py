@@ -1,6 +1,6 @@
 """config.ada_target without a GPU: the gate uniforms, the NumPy specification of the gate and of the controller (libml/ada.py),
-the configuration errors, the switch through ``train_step`` on the CPU operator table (tests/cpu_ops.py has neither ``ada_gate``
-nor ``ada_update``: the controller takes the specification), and the controller's state through a checkpoint."""
+the configuration errors, the switch through ``train_step`` on the CPU operator table (tests/cpu_ops.py: ``ada_gate`` in torch,
+``ada_update_rows`` by the specification), and the controller's state through a checkpoint."""
 import numpy as np
 import pytest
 import torch
@@ -123,7 +123,7 @@ def test_controller_gate_in_torch_equals_the_specification():
     ctl = ADA.AdaController("cpu")
     for p in (0.0, 0.3, 0.5, 1.0):
         ctl.state[0] = p
-        got = ctl.gate(object(), torch.from_numpy(plan), torch.from_numpy(u))
+        got = ctl.gate(CpuOps(), torch.from_numpy(plan), torch.from_numpy(u))      # (the torch gate is the CPU table's)
         assert got.is_contiguous() and got.numpy().tobytes() == ADA.gate(plan, u, p).tobytes()
 
 

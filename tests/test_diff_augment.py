@@ -1,6 +1,6 @@
 """config.diff_augment without a GPU: the policy parser, the plan's draws, the NumPy specification against its own adjoint in
 float64, the torch executors against autograd, the library's host-side plan validation, and the switch through ``train_step`` on
-the CPU operator table (tests/cpu_ops.py has no ``diff_augment``: the step takes the torch executors)."""
+the CPU operator table (tests/cpu_ops.py: ``diff_augment`` by the torch executors)."""
 import ctypes as C
 import itertools
 

@@ -1,6 +1,6 @@
 """config.lecam_weight without a GPU: the NumPy specification of the regulariser (libml/lecam.py) against float64 autograd, its state
-machine, the configuration errors, the switch through ``train_step`` on the CPU operator table (tests/cpu_ops.py has no ``lecam``:
-the controller takes the specification), and the controller's state through a checkpoint."""
+machine, the configuration errors, the switch through ``train_step`` on the CPU operator table (tests/cpu_ops.py: ``lecam_rows``
+by the specification), and the controller's state through a checkpoint."""
 import numpy as np
 import pytest
 import torch

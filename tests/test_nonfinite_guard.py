@@ -2,7 +2,7 @@
 step behind a skipped one is the clean step, only the bad half is skipped, the switch changes nothing on clean data, the training
 loop survives a poisoned batch (and stops after ``nonfinite_max_consecutive``), ``check_config`` and the replica refusal.
 
-Two tables: ``CpuOps`` (none of the new ops: the product's torch arithmetic, verdict read on the host) and ``CpuOpsGuard``
+Two tables: ``CpuOps`` (the verdict by ``torch.isfinite``, no device-side Adam: the verdict is read on the host) and ``CpuOpsGuard``
 (tests/cpu_ops_guard.py: the new entry points restated, Adam's t in a device-side counter).  The poison is a VALUE in an input tensor:
 ``z[row, 0] = NaN``."""
 import json

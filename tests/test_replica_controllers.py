@@ -1,6 +1,6 @@
 """config.ada_target, config.lecam_weight and config.skip_nonfinite_updates with data-parallel replicas, without a GPU
 (DESIGN.md 9f.3): the NumPy specifications of the three ``_rows`` kernels, ``GradSync.gather_rows`` and the refusals that stay,
-and two gloo ranks on the CPU operator table (which has none of the new ops: the controllers take the specifications)."""
+and two gloo ranks on the CPU operator table (whose ``_rows`` ops are the specifications)."""
 import os
 import socket
 import sys
@@ -81,7 +81,7 @@ def test_ada_update_rows_with_one_row_is_update():
 
 
 def _torch_rule(verdicts):
-    """the guard's own torch rule (operator tables without the op) over a sequence of single-rank verdicts"""
+    """the torch rule of the CPU operator table's ``nonfinite_verdict`` over a sequence of single-rank verdicts"""
     g, out = NG.NonfiniteGuard(torch.device("cpu")), []
     for bad_count, first in verdicts:
         seg = torch.ones(max(bad_count, 1))
@@ -236,9 +236,8 @@ def test_the_checks_still_refuse_anything_but_an_exclusive_exchange(key, one_ran
                 assert all(word in str(e.value) for word in ("replicas", key, "GradSync(schedule='exclusive')"))
         assert torch.equal(state.g_optimizer.arena.params, before[0]) and torch.equal(state.d_optimizer.arena.params, before[1])
         assert small and not any(t.any() for t in small)
-        for check in (xmc_gan.check_ada_replicas, xmc_gan.check_lecam_replicas, xmc_gan.check_guard_replicas):
-            check(cfg, None)
-            check(cfg, dp.GradSync(schedule="exclusive"))
+        xmc_gan.check_replica_controllers(cfg, None)
+        xmc_gan.check_replica_controllers(cfg, dp.GradSync(schedule="exclusive"))
     finally:
         xmc_net.set_ops_factory(None)
 

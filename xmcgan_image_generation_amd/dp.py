@@ -25,6 +25,16 @@ def check_schedule(schedule, bn_groups):
             "deadlock hazard")
 
 
+def logit_rows(logit, b, replicas=None, rows=None):
+    """-> (rows, rank): the (world, 2b) float32 rows that config.ada_target and config.lecam_weight are decided from, and the
+    row that is this replica's own.  ``replicas`` (the step's exclusive ``GradSync``): ``GradSync.logit_rows``.  Without: the
+    discriminator's (2b,) logit vector ``logit`` itself as ONE row -- a view, no copy and no launch"""
+    if replicas is not None:
+        return replicas.logit_rows(logit, b, rows), replicas.rank
+    assert logit.dtype == torch.float32 and logit.dim() == 1 and logit.is_contiguous()
+    return logit.detach()[:2 * int(b)].view(1, 2 * int(b)), 0
+
+
 class BNGroups:
     """The replica groups that share BatchNorm statistics (``config.batch_norm_group_size > 0``; flax
     ``nn.BatchNorm(axis_name="batch", axis_index_groups=get_device_groups(...))``, reference xmc_net.py:192-201).

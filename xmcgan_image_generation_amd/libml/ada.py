@@ -10,9 +10,9 @@ adjustment) / (``ada_kimg`` * 1000), clamped to [0, ``P_MAX``].
 
 This module is NumPy first: ``gate`` and ``update`` are the written specification of ``xmc_ada_gate`` / ``xmc_ada_update``
 (csrc/ada.hip).  Both are exact -- a select on a float64 comparison, integer counts, and five IEEE double operations in a fixed
-order -- so the kernels are held to them bit for bit.  ``AdaController`` owns the persistent state in device memory and runs the
-kernels where the operator table has them, the specification otherwise.  With data-parallel replicas the signs
-are counted over the all-gathered logits of every rank: ``update_rows`` is the specification of ``xmc_ada_update_rows``.
+order -- so the kernels are held to them bit for bit.  ``AdaController`` owns the persistent state in device memory and calls
+the operator table's ``ada_gate`` and ``ada_update_rows``.  The signs are counted over logit rows, one per replica
+(DESIGN.md 9f.3): ``update_rows`` is the specification of ``xmc_ada_update_rows``, bit-equal to ``xmc_ada_update`` with one row.
 """
 from __future__ import annotations
 
@@ -127,10 +127,8 @@ def update_rows(state, rows, b, target, images_to_full, interval, p_max) -> np.n
 
 class AdaController:
     """The controller's persistent ``float64[8]`` state in device memory (outside the step's pool, so a captured step replays
-    on it) and the two launches that use it.  On ``HipOps`` ``gate`` is ``xmc_ada_gate`` and ``update`` is ``xmc_ada_update``:
-    no host read, one graph launch per step stays true.  On an operator table without those ops the specification runs instead
-    (``update`` then reads the logits on the host: such a table is eager by construction).  ``read`` is the only
-    synchronisation of the product path."""
+    on it) and the two launches that use it.  On ``HipOps`` ``gate`` is ``xmc_ada_gate`` and ``update`` is
+    ``xmc_ada_update_rows``: no host read, one graph launch per step stays true.  ``read`` is the only synchronisation."""
 
     def __init__(self, device, config=None, p_max=P_MAX):
         import torch
@@ -142,37 +140,18 @@ class AdaController:
     def gate(self, ops, aug, u):
         """``aug``: the plan (B, 2, 8), ``u``: the uniforms (B, 2, 5), both float32 on the table's device -> rows (2B, 8)"""
         import torch
-        aug, u = aug.to(torch.float32).contiguous(), u.to(torch.float32).contiguous()
-        if hasattr(ops, "ada_gate"):
-            return ops.ada_gate(aug, u, self.state)
-        on = (u.double() < self.state[0].to(u.device))[..., list(PART_OF_COLUMN)]
-        ident = torch.tensor(diff_augment.IDENTITY_ROW, dtype=torch.float32, device=aug.device)
-        rows = torch.where(on, aug, ident)
-        return rows.transpose(0, 1).reshape(2 * aug.shape[0], diff_augment.PLAN_WIDTH).contiguous()
+        return ops.ada_gate(aug.to(torch.float32).contiguous(), u.to(torch.float32).contiguous(), self.state)
 
     def update(self, ops, logit, b, replicas=None, rows=None):
         """one half step: ``logit`` is D's (2B,) float32 logit vector, whose first ``b`` entries are the real half.  ``replicas``
         (the step's ``dp.GradSync``, exclusive schedule): the signs are counted over the real halves of ALL ranks' logits
-        (``GradSync.logit_rows``; ``rows``: already gathered), so every rank holds the same p"""
-        import torch
+        (``dp.logit_rows``; ``rows``: already gathered), so every rank holds the same p.  Without: over the one row ``logit``"""
+        from .. import dp
         if self.settings is None:
             raise ValueError("AdaController.update needs the controller's settings (built without a config)")
         s = self.settings
-        if replicas is not None:
-            rows = replicas.logit_rows(logit, b, rows)
-            if hasattr(ops, "ada_update_rows"):
-                ops.ada_update_rows(rows, b, self.state, s["target"], s["images_to_full"], s["interval"], self.p_max)
-                return
-            new = update_rows(self.state.cpu().numpy(), rows.float().cpu().numpy(), b, s["target"], s["images_to_full"],
-                              s["interval"], self.p_max)
-            self.state.copy_(torch.from_numpy(new))
-            return
-        if hasattr(ops, "ada_update"):
-            ops.ada_update(logit, b, self.state, s["target"], s["images_to_full"], s["interval"], self.p_max)
-            return
-        new = update(self.state.cpu().numpy(), logit.detach()[:b].float().cpu().numpy(), s["target"], s["images_to_full"],
-                     s["interval"], self.p_max)
-        self.state.copy_(torch.from_numpy(new))
+        rows, _ = dp.logit_rows(logit, b, replicas, rows)
+        ops.ada_update_rows(rows, b, self.state, s["target"], s["images_to_full"], s["interval"], self.p_max)
 
     # -------------------------------------------------------------------------------------------------- host side
     def read(self):

@@ -8,9 +8,8 @@ effect on the backward pass is ``dld += 2 * lambda / b * (logit - anchor)`` on t
 
 This module is NumPy first: ``step`` is the written specification of ``xmc_lecam`` (csrc/lecam.hip).  It is IEEE double arithmetic
 in a fixed order -- the sums included (``fixed_sum``) -- so the kernel is held to it bit for bit.  ``LecamController`` owns the
-persistent state in device memory and runs the kernel where the operator table has it, the specification otherwise.  With
-data-parallel replicas R and the anchors come from the all-gathered logits of every rank: ``step_rows`` is the
-specification of ``xmc_lecam_rows``.
+persistent state in device memory and calls the operator table's ``lecam_rows``.  R and the anchors come from logit rows, one per
+replica: ``step_rows`` is the specification of ``xmc_lecam_rows``, bit-equal to ``xmc_lecam`` with one row.
 
 ``lecam_decay`` = 0.99 is the paper's decay as far as it can be recalled here, and 0.3 (CIFAR scale) / 0.01 (ImageNet scale) are its
 weights: policy defaults, NOT tuned in this project.
@@ -174,9 +173,8 @@ def step_rows(state, rows, rank, dld, lam, decay, start, one_sided=False):
 
 class LecamController:
     """The regulariser's persistent ``float64[8]`` state in device memory (outside the step's pool, so a captured step replays on
-    it) and the one launch that uses it.  On ``HipOps`` ``apply`` is ``xmc_lecam``: no host read, one graph launch per step stays
-    true.  On an operator table without ``lecam`` the specification runs instead (it reads the logits on the host: such a table is
-    eager by construction).  ``read`` is the only synchronisation of the product path."""
+    it) and the one launch that uses it.  On ``HipOps`` ``apply`` is ``xmc_lecam_rows``: no host read, one graph launch per step
+    stays true.  ``read`` is the only synchronisation."""
 
     def __init__(self, device, config=None):
         import torch
@@ -187,28 +185,14 @@ class LecamController:
     def apply(self, ops, logit, dld, b, replicas=None, rows=None):
         """one half step: ``logit`` is D's (2B,) float32 logit vector [real; fake], ``dld`` the (2B,) float32 gradient the hinge
         launch has just written, which takes the term IN PLACE.  -> (1,) float32: the unweighted R.  ``replicas`` (the step's
-        ``dp.GradSync``, exclusive schedule): R and the anchors come from ALL ranks' logits (``GradSync.logit_rows``; ``rows``:
-        already gathered), so every rank holds the same anchors and reports the same R"""
-        import torch
+        ``dp.GradSync``, exclusive schedule): R and the anchors come from ALL ranks' logits (``dp.logit_rows``; ``rows``:
+        already gathered), so every rank holds the same anchors and reports the same R.  Without: from the one row ``logit``"""
+        from .. import dp
         if self.settings is None:
             raise ValueError("LecamController.apply needs the controller's settings (built without a config)")
         s = self.settings
-        if replicas is not None:
-            rows = replicas.logit_rows(logit, b, rows)
-            if hasattr(ops, "lecam_rows"):
-                return ops.lecam_rows(rows, replicas.rank, dld, b, self.state, s["weight"], s["decay"], s["start"], s["one_sided"])
-            new, grad, r = step_rows(self.state.cpu().numpy(), rows.float().cpu().numpy(), replicas.rank,
-                                     dld.detach().float().cpu().numpy(), s["weight"], s["decay"], s["start"], s["one_sided"])
-            self.state.copy_(torch.from_numpy(new))
-            dld.copy_(torch.from_numpy(grad))
-            return torch.from_numpy(np.asarray([r], np.float32)).to(dld.device)
-        if hasattr(ops, "lecam"):
-            return ops.lecam(logit, dld, b, self.state, s["weight"], s["decay"], s["start"], s["one_sided"])
-        new, grad, r = step(self.state.cpu().numpy(), logit.detach().float().cpu().numpy(), b, dld.detach().float().cpu().numpy(),
-                            s["weight"], s["decay"], s["start"], s["one_sided"])
-        self.state.copy_(torch.from_numpy(new))
-        dld.copy_(torch.from_numpy(grad))
-        return torch.from_numpy(np.asarray([r], np.float32)).to(dld.device)
+        rows, rank = dp.logit_rows(logit, b, replicas, rows)
+        return ops.lecam_rows(rows, rank, dld, b, self.state, s["weight"], s["decay"], s["start"], s["one_sided"])
 
     # -------------------------------------------------------------------------------------------------- host side
     def read(self):

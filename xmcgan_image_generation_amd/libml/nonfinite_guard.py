@@ -3,9 +3,8 @@
 ``NonfiniteGuard`` owns the device buffers of the decision: ``verdict`` (int32[4]: any bad value, how many, the first segment that
 held one, 0) written once per half step by ``judge``, and the persistent ``counters`` (int32[4]: half steps skipped in total, the
 current run of skipped ones, the longest run, padding) that travel in the checkpoint.  On ``HipOps`` ``judge`` is
-``xmc_nonfinite_verdict`` (two launches, no host read: a captured step replays it) and ``commit`` is ``xmc_commit_if``; on an operator
-table without those ops the same arithmetic runs in torch.  Nothing here reads the verdict on the host -- ``read`` (the training loop,
-at a logging boundary) is the only synchronisation.
+``xmc_nonfinite_verdict`` (two launches, no host read: a captured step replays it) and ``commit`` is ``xmc_commit_if``.  Nothing here
+reads the verdict on the host -- ``read`` (the training loop, at a logging boundary) is the only synchronisation.
 
 With data-parallel replicas (``judge(..., replicas=)``) the scan writes a local verdict, the ranks' verdicts are
 all-gathered and ``merge_rows`` -- the specification of ``xmc_verdict_merge`` -- turns the same rows into the same verdict and the
@@ -80,41 +79,21 @@ class NonfiniteGuard:
         if replicas is None:
             return self._scan(ops, segments, self.verdict, self.counters)
         rows = replicas.gather_rows(self._scan(ops, segments, self._local[0], self._local[1]))
-        if hasattr(ops, "verdict_merge"):
-            ops.verdict_merge(rows, self.verdict, self.counters)
-            return self.verdict
-        verdict, counters = merge_rows(rows.cpu().numpy(), self.counters.tolist())
-        self.verdict.copy_(torch.tensor(verdict, dtype=torch.int32))
-        self.counters.copy_(torch.tensor(counters, dtype=torch.int32))
+        ops.verdict_merge(rows, self.verdict, self.counters)
         return self.verdict
 
     def _scan(self, ops, segments, verdict, counters):
         """``xmc_nonfinite_verdict`` over ``segments`` into ``verdict`` / ``counters`` (int32[4] each) -> ``verdict``"""
-        if hasattr(ops, "nonfinite_verdict"):
-            if ops.nonfinite_verdict_ws_bytes([t.numel() for t in segments]) > self._ws.numel():
-                raise ValueError("NonfiniteGuard: the verdict's workspace is too small")
-            ops.nonfinite_verdict(segments, verdict, counters, self._ws)
-            return verdict
-        # the same arithmetic in torch (operator tables without the op)
-        bad, first = 0, -1
-        for i, t in enumerate(segments):
-            k = int((~torch.isfinite(t)).sum())
-            if k and first < 0:
-                first = i
-            bad += k
-        verdict.copy_(torch.tensor([int(bad > 0), min(bad, _INT32_MAX), first, 0], dtype=torch.int32))
-        counters.copy_(torch.tensor(advance_counters(counters.tolist(), bad), dtype=torch.int32))
+        if ops.nonfinite_verdict_ws_bytes([t.numel() for t in segments]) > self._ws.numel():
+            raise ValueError("NonfiniteGuard: the verdict's workspace is too small")
+        ops.nonfinite_verdict(segments, verdict, counters, self._ws)
         return verdict
 
     def commit(self, ops, dst, src):
         """dst = src unless the verdict is bad"""
         if dst.data_ptr() == src.data_ptr():
             return dst
-        if hasattr(ops, "commit_if"):
-            return ops.commit_if(dst, src.contiguous(), self.verdict)
-        if int(self.verdict[0]) == 0:
-            dst.copy_(src)
-        return dst
+        return ops.commit_if(dst, src.contiguous(), self.verdict)
 
     # -------------------------------------------------------------------------------------------------- host side
     def read(self):

@@ -153,10 +153,7 @@ def train_step(rng, state, batch, gan_model=xmc_gan, generator=None, discriminat
     ``d_aug_host`` (config.diff_augment): the host copy of ``batch["d_aug"]`` when that is a device tensor the caller cannot have
     read back here (``GraphedTrainStep``'s capture); otherwise it is made from the batch."""
     n = config.d_step_per_g_step
-    xmc_gan.check_guard_replicas(config, grad_sync)
-    if gan_model is xmc_gan:
-        xmc_gan.check_ada_replicas(config, grad_sync)
-        xmc_gan.check_lecam_replicas(config, grad_sync)
+    xmc_gan.check_replica_controllers(config, grad_sync)
     if grad_sync is not None and config.get("batch_norm_group_size", -1) > 0:
         grad_sync.require_groups(generator(train=True).bn_groups)
     parts = split_input_dict(batch, n)
